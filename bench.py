@@ -1,6 +1,18 @@
 """Benchmark of the PPG hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4] [--precision bf16|fp16|fp32]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, ...).  Everything else -- the roofline
+leg, repeat blocks, shader clock, per-kernel breakdown, host copies, the other precisions and configurations, the
+dense-MFMA probe, the CPU baseline, C4's gatherv -- runs only with ``--full`` and adds its fields to the same line.
+
+``--dump-outputs DIR``: after the timed steps, what the timed path computed in its LAST step is written as
+DIR/<name>.npy (float32; rank 0's): C2 the whole (32, 40, 1000) posteriors as `ppg`; C4 the posteriors of a fixed,
+seeded sample of the pass's batches (at most 48 MiB) as `ppg_sample` (40, frames), the utterances concatenated, with their
+corpus indices and frame counts (`ppg_sample_utterances`, `ppg_sample_frames`, float64).  The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 
 Default workload = BASELINE.json configs[1] ("c2"): one step = one pass of the
 whole hot path over one batch of synthetic input that is already resident in
@@ -32,7 +44,7 @@ load below its sustained clocks (tools/clock_series.py; round 2: the first 20-st
 block 0.837 ms/step, the next two 0.771 / 0.765 on the same box).  ``--prewarm-s 0``
 with ``--warmup 5`` times that ramp.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the
+Rank 0 prints ONE JSON line.  With --full: `roofline` is for the dominant kernel (the
 layer kernel): algorithmic FLOPs per launch / its mean launch duration
 measured with HIP events on the launch stream inside the timed region, priced
 against the WHOLE chip's dense MFMA peak (`roofline.frac`).
@@ -72,6 +84,18 @@ HIDDEN, FFN, LAYERS = 256, 2048, 5
 # bookkeeping (sharding, barriers, the gatherv, the record's fields) over gloo with a stub engine -- no such record is a
 # measurement, and the engine itself has no CPU path
 DEVICE = 'cuda'
+DUMP_SAMPLE_BYTES = 48 << 20   # --dump-outputs, c4: posteriors of the sampled batches' utterances stay below this
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy, float32 (float64 arrays stay float64)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, value in arrays.items():
+        if torch.is_tensor(value):
+            value = value.detach().cpu().numpy()
+        assert value.dtype in (np.float32, np.float64), (name, value.dtype)
+        np.save(os.path.join(directory, name + '.npy'), value)
 
 
 # PPGS_AMD_* switches that select a CONFIGURATION of the same computed work (recorded in the line as `env_switches`);
@@ -192,13 +216,19 @@ def parse(argv=None):
     parser.add_argument('--workload', default='c2', choices=['c2', 'c4'])
     parser.add_argument('--precision', default='bf16', choices=['bf16', 'fp16', 'fp32', 'fp16x2'])
     parser.add_argument('--utterances', type=int, default=10000, help='c4: corpus size')
+    parser.add_argument('--full', action='store_true',
+                        help='also run every leg beside the headline figure (roofline, repeat blocks, clock, per-kernel '
+                             'breakdown, host copies, other precisions / configurations, MFMA probe, CPU baseline, '
+                             'C4 gatherv) and add its fields to the line')
+    parser.add_argument('--dump-outputs', metavar='DIR', default=None,
+                        help='write what the timed path computed in its last step to DIR/<name>.npy (float32)')
     parser.add_argument('--cpu-seconds', type=float, default=20.0,
-                        help='budget of the CPU-baseline leg')
-    parser.add_argument('--no-cpu', action='store_true')
+                        help='budget of the CPU-baseline leg (--full)')
+    parser.add_argument('--no-cpu', action='store_true', help='--full without the CPU-baseline leg')
     parser.add_argument('--allow-ablation', action='store_true',
                         help='run although PPGS_AMD_* experiment switches are set; the line then carries them under '
                              '`ablation_env` and its `value` is null')
-    parser.add_argument('--no-alt', action='store_true', help='skip the fp16-operand leg of c2')
+    parser.add_argument('--no-alt', action='store_true', help='--full without the other-precision / configuration legs of c2')
     parser.add_argument('--prewarm-s', type=float, default=1.0,
                         help='c2: seconds of the same step run untimed after the W warm-up steps and before the '
                              'timed K steps (the metric is the steady-state loop; a GPU that has been idle '
@@ -418,174 +448,31 @@ def run_c2(args, rank, world, local_rank, use_dist):
     # (the first torch kernel of the process loads torch's code objects: tens of milliseconds of idle GPU --
     # here, not between the warm-up and the timed region)
     assert out.shape == (BATCH, 40, FRAMES) and bool(torch.isfinite(out).all())
-    # the events of the roofline leg exist before the timed region starts
-    model.profile(True, classes=['ffn'], stride=EVENT_STRIDE)
-    for _ in range(6):
-        step()
-    torch.cuda.synchronize()
-    model.profile_read()
+    if args.full:
+        # the events of the roofline leg exist before the timed region starts
+        model.profile(True, classes=['ffn'], stride=EVENT_STRIDE)
+        for _ in range(6):
+            step()
+        torch.cuda.synchronize()
+        model.profile_read()
     barrier()                            # (N > 1: RCCL builds its communicator on the first collective, not in the timed region)
     # Nothing may idle the GPU between here and the timed region: after ~1 ms without work the chip drops its
     # clocks and needs ~16 ms of load to get them back (tools/clock_series.py: first 20-step block after an idle
     # gap 0.81 - 0.83 ms/step, every later one 0.74) -- a 20-step timed region IS 16 ms.
     prewarm_steps, prewarm_seconds = prewarm()
-    model.profile(True, classes=['ffn'], stride=EVENT_STRIDE)         # (reset of the counters: two ctypes calls)
+    if args.full:
+        model.profile(True, classes=['ffn'], stride=EVENT_STRIDE)     # (reset of the counters: two ctypes calls)
 
-    # timed region: HIP events only around the dominant kernel (roofline leg)
+    # timed region; with --full, HIP events only around the dominant kernel (roofline leg)
     # (every 6th launch: 6 is coprime with the 5 layers, so the samples rotate
     # through the five launches of a step; two event records per launch cost
     # ~1.5 us each on the stream, 1.5 % of the step if every launch is timed)
     elapsed, out = timed_block()
     rank_ms = [1e3 * t / args.steps for t in per_rank]
-    ffn_ms, ffn_samples = model.profile_read()['ffn']
-    model.profile(False)
-    # two more blocks of the same K steps: how much the figure moves from block to block
-    repeats = [1e3 * timed_block()[0] / args.steps for _ in range(2)]
-    # the shader clock while the same block of steps runs once more (untimed; a sampler thread reads sysfs)
-    with ClockSampler(local_rank) as sampler:
-        timed_block()
-    clock = sampler.summary()
-    # untimed extra pass: per-kernel-class breakdown (events around every launch)
-    breakdown_steps = 5
-    model.profile(True)
-    E.frontend_profile(local_rank, True)
-    for _ in range(breakdown_steps):
-        step()
-    torch.cuda.synchronize()
-    kernels = model.profile_read()
-    kernels['frontend'] = E.frontend_profile_read(local_rank)
-    model.profile(False)
-    E.frontend_profile(local_rank, False)
-
-    # host <-> device legs, timed on their own (never part of `value`): pinned audio H2D, posteriors D2H
-    host_out = torch.empty(out.shape, dtype=out.dtype).pin_memory()
-    copies = {}
-    for name, fn in (('h2d_ms', lambda: audio.copy_(host_audio, non_blocking=True)),
-                     ('d2h_ms', lambda: host_out.copy_(out, non_blocking=True))):
-        fn()
-        torch.cuda.synchronize()
-        start = time.perf_counter()
-        for _ in range(10):
-            fn()
-        torch.cuda.synchronize()
-        copies[name] = 1e3 * (time.perf_counter() - start) / 10
-
-    alt = alt_x2 = None
-    if rank == 0 and world == 1 and not args.no_alt and args.precision == 'bf16':
-        # the same step with fp16 MFMA operands (same MFMA rate, 8x smaller operand rounding)
-        other = E.Engine(state, local_rank, 'fp16')
-        for _ in range(max(args.warmup, 3)):
-            step(other)
-        prewarm(other)
-        alt_elapsed, alt_out = timed_block(other)
-        alt = {'dtype': 'fp16 operands, fp32 accumulate', 'ms_per_step': 1e3 * alt_elapsed / args.steps,
-               'value': BATCH * FRAMES * args.steps / alt_elapsed,
-               'max_abs_vs_bf16': float((alt_out - out).abs().max())}
-        del other
-        # ... and with split operands (fp16 hi + lo planes, three MFMAs per product): the mode that meets the north
-        # star's 1e-4 (measured 3e-6 against the fp32 oracle) without the f32-input MFMAs' 1/16 rate
-        other = E.Engine(state, local_rank, 'fp16x2')
-        for _ in range(max(args.warmup, 3)):
-            step(other)
-        prewarm(other)
-        x2_elapsed, x2_out = timed_block(other)
-        alt_x2 = {'dtype': 'fp16x2: fp32 values as fp16 hi + lo, 3 fp16 MFMAs per product, fp32 accumulate',
-                  'ms_per_step': 1e3 * x2_elapsed / args.steps, 'value': BATCH * FRAMES * args.steps / x2_elapsed,
-                  'end_to_end_tflops_algorithmic': BATCH * data.flops(FRAMES) * args.steps / x2_elapsed / 1e12,
-                  'max_abs_vs_fp16': float((x2_out - alt_out).abs().max())}
-        # matrix-pipe busy cycles of an fp16x2 step (three MFMAs per product) from the committed PMC pass of this build
-        # with --precision fp16x2, over 4 pipes x CUs x this leg's step time at the nominal 2.4 GHz
-        x2_pmc, x2_from = pmc_summary('_fp16x2', 'fp16x2')
-        x2_busy = pmc_mfma_busy(x2_pmc) if x2_pmc else None
-        alt_x2['mfma_busy_cycles_per_step'] = x2_busy
-        alt_x2['mfma_busy_frac'] = (x2_busy / (4.0 * torch.cuda.get_device_properties(local_rank).multi_processor_count
-                                               * alt_x2['ms_per_step'] * 2.4e6)) if x2_busy else None
-        alt_x2['mfma_busy_from'] = x2_from
-        del other
-    alt_streams = None
-    _, info = E.plan_windows(BATCH, FRAMES, lengths)
-    pipelines = model.pipelines(info.tokens)
-    if rank == 0 and world == 1 and not args.no_alt and 'PPGS_AMD_STREAMS' not in os.environ and pipelines > 1:
-        # the same step as ONE pipeline (PPGS_AMD_STREAMS=1): every launch then has the whole chip to itself, which is
-        # the configuration a per-kernel whole-chip roofline fraction can be read from; it is the slower one (the
-        # half-batches' memory-bound phases no longer run beside each other's MFMA phases), so it is not the default.
-        os.environ['PPGS_AMD_STREAMS'] = '1'
-        try:
-            other = E.Engine(state, local_rank, args.precision)
-        finally:
-            del os.environ['PPGS_AMD_STREAMS']
-        for _ in range(max(args.warmup, 3)):
-            step(other)
-        prewarm(other)
-        other.profile(True, classes=['ffn'], stride=EVENT_STRIDE)
-        s1_elapsed, s1_out = timed_block(other)
-        s1_ms, s1_samples = other.profile_read()['ffn']
-        other.profile(False)
-        alt_streams = {'pipelines': 1, 'ms_per_step': 1e3 * s1_elapsed / args.steps,
-                       'value': BATCH * FRAMES * args.steps / s1_elapsed,
-                       'mean_launch_ms': s1_ms / max(s1_samples, 1), 'timed_launches': s1_samples,
-                       'max_abs_vs_default': float((s1_out - out).abs().max())}
-        del other
-
-    alt_graph = None
-    if rank == 0 and world == 1 and not args.no_alt:
-        # the same step with the encoder's launch sequence (both pipelines, their fork / join) as ONE hipGraph replay
-        # (Engine.graphed; the mel frontend launched in front of it as before).  Reported beside the line, never `value`:
-        # the timed region above is the eager path, whose launches the roofline leg's HIP events can bracket.
-        try:
-            replay = model.graphed(BATCH, FRAMES, lengths)
-
-            def graph_step():
-                return replay(ppgs_amd.preprocess.mel.from_audios(audio))
-            for _ in range(max(args.warmup, 3)):
-                graph_step()
-            start = time.perf_counter()
-            while args.prewarm_s > 0 and time.perf_counter() - start < args.prewarm_s:
-                for _ in range(20):
-                    graph_step()
-                torch.cuda.synchronize()
-            torch.cuda.synchronize()
-            start = time.perf_counter()
-            for _ in range(args.steps):
-                g_out = graph_step()
-            torch.cuda.synchronize()
-            g_elapsed = time.perf_counter() - start
-            alt_graph = {'what': 'encoder as one hipGraph replay per step (Engine.graphed), frontend in front of it',
-                         'ms_per_step': 1e3 * g_elapsed / args.steps, 'value': BATCH * FRAMES * args.steps / g_elapsed,
-                         'max_abs_vs_default': float((g_out - out).abs().max())}
-            del replay
-        except Exception as error:                              # the leg is optional: the line must not depend on it
-            alt_graph = {'skipped': f'{type(error).__name__}: {error}'}
-
-    if rank != 0:
-        return None
     ms_per_step = 1e3 * elapsed / args.steps
     frames_per_s = world * BATCH * FRAMES * args.steps / elapsed
-    launches_per_layer = max(kernels['ffn'][1] // (LAYERS * breakdown_steps), 1)
-    flops_per_frame, op_fused, qkv_fused_layers = layer_flops_per_frame(kernels, breakdown_steps, launches_per_layer)
-    ffn_flops = flops_per_frame * info.processed_frames / launches_per_layer
-    ffn_tflops = ffn_flops / (1e-3 * ffn_ms / max(ffn_samples, 1)) / 1e12
     peak = PEAK_FP32_TFLOPS if args.precision == 'fp32' else PEAK_16BIT_TFLOPS
     step_flops = BATCH * data.flops(FRAMES)
-    # CUs a launch of the dominant kernel can occupy: one workgroup per CU (its LDS tile), one workgroup per token tile
-    launch_workgroups = None
-    x2 = args.precision == 'fp16x2'                     # ffn32x2_kernel: 96-token tiles
-    layer32 = args.precision in ('bf16', 'fp16') and os.environ.get('PPGS_AMD_LAYER32', '1') != '0'
-    if layer32 or x2:
-        launch_workgroups = -(-info.tokens // (96 if x2 else 160)) // launches_per_layer
-    cus = torch.cuda.get_device_properties(local_rank).multi_processor_count
-    launch_cus = min(launch_workgroups, cus) if launch_workgroups else cus
-    launch_peak = peak * launch_cus / cus
-    pmc, pmc_from = pmc_summary('_fp16x2' if x2 else '', args.precision)
-    traffic = pmc_traffic(pmc, 'ffn32x2_' if x2 else ('layer32_' if layer32 else 'ffn_')) if pmc else None
-    mfma_busy = pmc_mfma_busy(pmc) if pmc else None
-    kernel_name = ('ffn32x2_kernel (feature-split layer kernel on fp16 hi + lo operand pairs, three v_mfma_f32_32x32x16_f16 '
-                   'per product: out-proj+residual+LN1, W1+ReLU+W2+residual+LN2, next layer Q/K/V)') if x2 else (
-                   'layer32_kernel (feature-split layer kernel on v_mfma_f32_32x32x16: out-proj+residual+LN1, '
-                   'W1+ReLU+W2+residual+LN2' + (', next layer Q/K/V)' if qkv_fused_layers else ')')) if layer32 else (
-        'ffn_mixed_kernel (token-split layer kernel: out-proj+residual+LN1, W1+ReLU+W2+residual+LN2'
-        + (', next layer Q/K/V)' if qkv_fused_layers else ')') if op_fused
-        else 'ffn_kernel (fused W1+ReLU+W2+residual+LayerNorm)')
     line = {
         'metric': 'PPG frames/sec (whole node), mel repr, batch=32x1000 frames',
         'value': frames_per_s,
@@ -611,77 +498,226 @@ def run_c2(args, rank, world, local_rank, use_dist):
             'batch': BATCH, 'frames': FRAMES, 'per_gpu_batches': 1,
             'parallelism': f'utterance-sharded x{world}, no data-path collective',
         },
-        'roofline': {
-            'kernel': kernel_name,
-            'bound': 'mfma',
-            'achieved': ffn_tflops,
-            'peak': peak,
-            'unit': 'TFLOP/s',
-            'frac': ffn_tflops / peak,
-            'peak_scope': f'whole chip ({cus} CUs, dense {args.precision} MFMA peak of MI355X_MICROARCH.md).  A launch is '
-                          f'{launch_workgroups or "?"} workgroups, one per CU, and {pipelines} pipeline(s) of the batch run '
-                          'beside each other: `achieved` is ONE launch\'s FLOPs over its own duration while the other '
-                          'pipeline\'s kernels share the chip -- the step as a whole is end_to_end_mfma_frac, and '
-                          'alt_single_pipeline has the per-launch figure with the chip to itself',
-            'frac_of_occupied_cus': ffn_tflops / launch_peak,
-            'occupied_cus': launch_cus,
-            'pipelines': pipelines,
-            'traffic': traffic,
-            'traffic_from': f'{pmc_from} (committed rocprofv3 --pmc passes of this command and this build, not this run)'
-                            if pmc else pmc_from,
-            'flops_per_launch': ffn_flops,
-            'mean_launch_ms': ffn_ms / max(ffn_samples, 1),
-            'timed_launches': ffn_samples,
-        },
         'end_to_end_tflops': step_flops * args.steps / elapsed / 1e12,
         'end_to_end_mfma_frac': step_flops * args.steps / elapsed / 1e12 / peak,
-        # HIP-event durations summed over BOTH pipelines' streams: with two pipelines the classes overlap in time and
-        # the sum exceeds the step (divide a class by `pipelines` for its share of the wall clock, roughly)
-        'kernel_ms_per_step_stream_summed': {k: v[0] / breakdown_steps for k, v in kernels.items()},
-        'kernel_ms_pipelines': pipelines,
-        # matrix-pipe busy cycles of a step (all kernels, rocprofv3 SQ_VALU_MFMA_BUSY_CYCLES of the committed PMC pass
-        # of this build) over 4 pipes x CUs x the step's duration at the nominal 2.4 GHz the 2.5 PF peak is quoted at
-        'mfma_busy_cycles_per_step': mfma_busy,
-        'mfma_busy_frac': mfma_busy / (4.0 * cus * ms_per_step * 2.4e6) if mfma_busy else None,
-        # the shader clock sampled while one more block of the same K steps ran, and the same busy cycles over the
-        # cycles that clock DELIVERED in a step (the pipes are busier than the nominal-clock fraction says when the chip
-        # runs below 2.4 GHz)
-        'shader_clock_under_load': clock,
-        'mfma_busy_frac_of_delivered_cycles': (mfma_busy / (4.0 * cus * ms_per_step * 1e3 * clock['mean_mhz'])
-                                               if mfma_busy and clock else None),
         'env_switches': args.env_config,
-        'repeat_blocks_ms_per_step': repeats,
-        'h2d_ms': copies['h2d_ms'],
-        'd2h_ms': copies['d2h_ms'],
-        'pcie_inclusive_ms_per_step': ms_per_step + copies['h2d_ms'] + copies['d2h_ms'],
     }
-    if alt:
-        line['alt_precision'] = alt
-    if alt_x2:
-        line['alt_precision_fp16x2'] = alt_x2
-    if alt_streams:
-        # the one-pipeline run's layer launches are whole-batch launches on the whole chip
-        alt_streams['roofline_frac_whole_chip'] = (ffn_flops * launches_per_layer / (1e-3 * alt_streams['mean_launch_ms'])
-                                                   / 1e12 / peak)
-        line['alt_single_pipeline'] = alt_streams
-    if alt_graph:
-        line['alt_graph_replay'] = alt_graph
-    if rank == 0 and world == 1:
-        probe = dense_mfma_probe()
-        line['dense_mfma_probe'] = probe
-        if probe and args.precision != 'fp32':
-            # the same fractions against what the probe measured on THIS box instead of the nominal 2.5 PFLOP/s
-            delivered = probe['dense']['tflops']
-            line['roofline']['frac_of_delivered_dense_peak'] = ffn_tflops / delivered
-            line['end_to_end_frac_of_delivered_dense_peak'] = line['end_to_end_tflops'] / delivered
-    if world == 1 and not args.no_cpu:
-        line['cpu_baseline'] = cpu_baseline(state, args.cpu_seconds)
-        line['speedup_vs_cpu'] = frames_per_s / line['cpu_baseline']['value']
+    if args.full:
+        ffn_ms, ffn_samples = model.profile_read()['ffn']
+        model.profile(False)
+        # two more blocks of the same K steps: how much the figure moves from block to block
+        repeats = [1e3 * timed_block()[0] / args.steps for _ in range(2)]
+        # the shader clock while the same block of steps runs once more (untimed; a sampler thread reads sysfs)
+        with ClockSampler(local_rank) as sampler:
+            timed_block()
+        clock = sampler.summary()
+        # untimed extra pass: per-kernel-class breakdown (events around every launch)
+        breakdown_steps = 5
+        model.profile(True)
+        E.frontend_profile(local_rank, True)
+        for _ in range(breakdown_steps):
+            step()
+        torch.cuda.synchronize()
+        kernels = model.profile_read()
+        kernels['frontend'] = E.frontend_profile_read(local_rank)
+        model.profile(False)
+        E.frontend_profile(local_rank, False)
+
+        # host <-> device legs, timed on their own (never part of `value`): pinned audio H2D, posteriors D2H
+        host_out = torch.empty(out.shape, dtype=out.dtype).pin_memory()
+        copies = {}
+        for name, fn in (('h2d_ms', lambda: audio.copy_(host_audio, non_blocking=True)),
+                         ('d2h_ms', lambda: host_out.copy_(out, non_blocking=True))):
+            fn()
+            torch.cuda.synchronize()
+            start = time.perf_counter()
+            for _ in range(10):
+                fn()
+            torch.cuda.synchronize()
+            copies[name] = 1e3 * (time.perf_counter() - start) / 10
+
+        alt = alt_x2 = None
+        if rank == 0 and world == 1 and not args.no_alt and args.precision == 'bf16':
+            # the same step with fp16 MFMA operands (same MFMA rate, 8x smaller operand rounding)
+            other = E.Engine(state, local_rank, 'fp16')
+            for _ in range(max(args.warmup, 3)):
+                step(other)
+            prewarm(other)
+            alt_elapsed, alt_out = timed_block(other)
+            alt = {'dtype': 'fp16 operands, fp32 accumulate', 'ms_per_step': 1e3 * alt_elapsed / args.steps,
+                   'value': BATCH * FRAMES * args.steps / alt_elapsed,
+                   'max_abs_vs_bf16': float((alt_out - out).abs().max())}
+            del other
+            # ... and with split operands (fp16 hi + lo planes, three MFMAs per product): the mode that meets the north
+            # star's 1e-4 (measured 3e-6 against the fp32 oracle) without the f32-input MFMAs' 1/16 rate
+            other = E.Engine(state, local_rank, 'fp16x2')
+            for _ in range(max(args.warmup, 3)):
+                step(other)
+            prewarm(other)
+            x2_elapsed, x2_out = timed_block(other)
+            alt_x2 = {'dtype': 'fp16x2: fp32 values as fp16 hi + lo, 3 fp16 MFMAs per product, fp32 accumulate',
+                      'ms_per_step': 1e3 * x2_elapsed / args.steps, 'value': BATCH * FRAMES * args.steps / x2_elapsed,
+                      'end_to_end_tflops_algorithmic': BATCH * data.flops(FRAMES) * args.steps / x2_elapsed / 1e12,
+                      'max_abs_vs_fp16': float((x2_out - alt_out).abs().max())}
+            # matrix-pipe busy cycles of an fp16x2 step (three MFMAs per product) from the committed PMC pass of this build
+            # with --precision fp16x2, over 4 pipes x CUs x this leg's step time at the nominal 2.4 GHz
+            x2_pmc, x2_from = pmc_summary('_fp16x2', 'fp16x2')
+            x2_busy = pmc_mfma_busy(x2_pmc) if x2_pmc else None
+            alt_x2['mfma_busy_cycles_per_step'] = x2_busy
+            alt_x2['mfma_busy_frac'] = (x2_busy / (4.0 * torch.cuda.get_device_properties(local_rank).multi_processor_count
+                                                   * alt_x2['ms_per_step'] * 2.4e6)) if x2_busy else None
+            alt_x2['mfma_busy_from'] = x2_from
+            del other
+        alt_streams = None
+        _, info = E.plan_windows(BATCH, FRAMES, lengths)
+        pipelines = model.pipelines(info.tokens)
+        if rank == 0 and world == 1 and not args.no_alt and 'PPGS_AMD_STREAMS' not in os.environ and pipelines > 1:
+            # the same step as ONE pipeline (PPGS_AMD_STREAMS=1): every launch then has the whole chip to itself, which is
+            # the configuration a per-kernel whole-chip roofline fraction can be read from; it is the slower one (the
+            # half-batches' memory-bound phases no longer run beside each other's MFMA phases), so it is not the default.
+            os.environ['PPGS_AMD_STREAMS'] = '1'
+            try:
+                other = E.Engine(state, local_rank, args.precision)
+            finally:
+                del os.environ['PPGS_AMD_STREAMS']
+            for _ in range(max(args.warmup, 3)):
+                step(other)
+            prewarm(other)
+            other.profile(True, classes=['ffn'], stride=EVENT_STRIDE)
+            s1_elapsed, s1_out = timed_block(other)
+            s1_ms, s1_samples = other.profile_read()['ffn']
+            other.profile(False)
+            alt_streams = {'pipelines': 1, 'ms_per_step': 1e3 * s1_elapsed / args.steps,
+                           'value': BATCH * FRAMES * args.steps / s1_elapsed,
+                           'mean_launch_ms': s1_ms / max(s1_samples, 1), 'timed_launches': s1_samples,
+                           'max_abs_vs_default': float((s1_out - out).abs().max())}
+            del other
+
+        alt_graph = None
+        if rank == 0 and world == 1 and not args.no_alt:
+            # the same step with the encoder's launch sequence (both pipelines, their fork / join) as ONE hipGraph replay
+            # (Engine.graphed; the mel frontend launched in front of it as before).  Reported beside the line, never `value`:
+            # the timed region above is the eager path, whose launches the roofline leg's HIP events can bracket.
+            try:
+                replay = model.graphed(BATCH, FRAMES, lengths)
+
+                def graph_step():
+                    return replay(ppgs_amd.preprocess.mel.from_audios(audio))
+                for _ in range(max(args.warmup, 3)):
+                    graph_step()
+                start = time.perf_counter()
+                while args.prewarm_s > 0 and time.perf_counter() - start < args.prewarm_s:
+                    for _ in range(20):
+                        graph_step()
+                    torch.cuda.synchronize()
+                torch.cuda.synchronize()
+                start = time.perf_counter()
+                for _ in range(args.steps):
+                    g_out = graph_step()
+                torch.cuda.synchronize()
+                g_elapsed = time.perf_counter() - start
+                alt_graph = {'what': 'encoder as one hipGraph replay per step (Engine.graphed), frontend in front of it',
+                             'ms_per_step': 1e3 * g_elapsed / args.steps, 'value': BATCH * FRAMES * args.steps / g_elapsed,
+                             'max_abs_vs_default': float((g_out - out).abs().max())}
+                del replay
+            except Exception as error:                              # the leg is optional: the line must not depend on it
+                alt_graph = {'skipped': f'{type(error).__name__}: {error}'}
+
+        if rank == 0:
+            launches_per_layer = max(kernels['ffn'][1] // (LAYERS * breakdown_steps), 1)
+            flops_per_frame, op_fused, qkv_fused_layers = layer_flops_per_frame(kernels, breakdown_steps, launches_per_layer)
+            ffn_flops = flops_per_frame * info.processed_frames / launches_per_layer
+            ffn_tflops = ffn_flops / (1e-3 * ffn_ms / max(ffn_samples, 1)) / 1e12
+            # CUs a launch of the dominant kernel can occupy: one workgroup per CU (its LDS tile), one workgroup per token tile
+            launch_workgroups = None
+            x2 = args.precision == 'fp16x2'                     # ffn32x2_kernel: 96-token tiles
+            layer32 = args.precision in ('bf16', 'fp16') and os.environ.get('PPGS_AMD_LAYER32', '1') != '0'
+            if layer32 or x2:
+                launch_workgroups = -(-info.tokens // (96 if x2 else 160)) // launches_per_layer
+            cus = torch.cuda.get_device_properties(local_rank).multi_processor_count
+            launch_cus = min(launch_workgroups, cus) if launch_workgroups else cus
+            launch_peak = peak * launch_cus / cus
+            pmc, pmc_from = pmc_summary('_fp16x2' if x2 else '', args.precision)
+            traffic = pmc_traffic(pmc, 'ffn32x2_' if x2 else ('layer32_' if layer32 else 'ffn_')) if pmc else None
+            mfma_busy = pmc_mfma_busy(pmc) if pmc else None
+            kernel_name = ('ffn32x2_kernel (feature-split layer kernel on fp16 hi + lo operand pairs, three v_mfma_f32_32x32x16_f16 '
+                           'per product: out-proj+residual+LN1, W1+ReLU+W2+residual+LN2, next layer Q/K/V)') if x2 else (
+                           'layer32_kernel (feature-split layer kernel on v_mfma_f32_32x32x16: out-proj+residual+LN1, '
+                           'W1+ReLU+W2+residual+LN2' + (', next layer Q/K/V)' if qkv_fused_layers else ')')) if layer32 else (
+                'ffn_mixed_kernel (token-split layer kernel: out-proj+residual+LN1, W1+ReLU+W2+residual+LN2'
+                + (', next layer Q/K/V)' if qkv_fused_layers else ')') if op_fused
+                else 'ffn_kernel (fused W1+ReLU+W2+residual+LayerNorm)')
+            line.update({
+                'roofline': {
+                    'kernel': kernel_name,
+                    'bound': 'mfma',
+                    'achieved': ffn_tflops,
+                    'peak': peak,
+                    'unit': 'TFLOP/s',
+                    'frac': ffn_tflops / peak,
+                    'peak_scope': f'whole chip ({cus} CUs, dense {args.precision} MFMA peak of MI355X_MICROARCH.md).  A launch is '
+                                  f'{launch_workgroups or "?"} workgroups, one per CU, and {pipelines} pipeline(s) of the batch run '
+                                  'beside each other: `achieved` is ONE launch\'s FLOPs over its own duration while the other '
+                                  'pipeline\'s kernels share the chip -- the step as a whole is end_to_end_mfma_frac, and '
+                                  'alt_single_pipeline has the per-launch figure with the chip to itself',
+                    'frac_of_occupied_cus': ffn_tflops / launch_peak,
+                    'occupied_cus': launch_cus,
+                    'pipelines': pipelines,
+                    'traffic': traffic,
+                    'traffic_from': f'{pmc_from} (committed rocprofv3 --pmc passes of this command and this build, not this run)'
+                                    if pmc else pmc_from,
+                    'flops_per_launch': ffn_flops,
+                    'mean_launch_ms': ffn_ms / max(ffn_samples, 1),
+                    'timed_launches': ffn_samples,
+                },
+                # HIP-event durations summed over BOTH pipelines' streams: with two pipelines the classes overlap in time and
+                # the sum exceeds the step (divide a class by `pipelines` for its share of the wall clock, roughly)
+                'kernel_ms_per_step_stream_summed': {k: v[0] / breakdown_steps for k, v in kernels.items()},
+                'kernel_ms_pipelines': pipelines,
+                # matrix-pipe busy cycles of a step (all kernels, rocprofv3 SQ_VALU_MFMA_BUSY_CYCLES of the committed PMC pass
+                # of this build) over 4 pipes x CUs x the step's duration at the nominal 2.4 GHz the 2.5 PF peak is quoted at
+                'mfma_busy_cycles_per_step': mfma_busy,
+                'mfma_busy_frac': mfma_busy / (4.0 * cus * ms_per_step * 2.4e6) if mfma_busy else None,
+                # the shader clock sampled while one more block of the same K steps ran, and the same busy cycles over the
+                # cycles that clock DELIVERED in a step (the pipes are busier than the nominal-clock fraction says when the chip
+                # runs below 2.4 GHz)
+                'shader_clock_under_load': clock,
+                'mfma_busy_frac_of_delivered_cycles': (mfma_busy / (4.0 * cus * ms_per_step * 1e3 * clock['mean_mhz'])
+                                                       if mfma_busy and clock else None),
+                'repeat_blocks_ms_per_step': repeats,
+                'h2d_ms': copies['h2d_ms'],
+                'd2h_ms': copies['d2h_ms'],
+                'pcie_inclusive_ms_per_step': ms_per_step + copies['h2d_ms'] + copies['d2h_ms'],
+            })
+            if alt:
+                line['alt_precision'] = alt
+            if alt_x2:
+                line['alt_precision_fp16x2'] = alt_x2
+            if alt_streams:
+                # the one-pipeline run's layer launches are whole-batch launches on the whole chip
+                alt_streams['roofline_frac_whole_chip'] = (ffn_flops * launches_per_layer / (1e-3 * alt_streams['mean_launch_ms'])
+                                                           / 1e12 / peak)
+                line['alt_single_pipeline'] = alt_streams
+            if alt_graph:
+                line['alt_graph_replay'] = alt_graph
+            if rank == 0 and world == 1:
+                probe = dense_mfma_probe()
+                line['dense_mfma_probe'] = probe
+                if probe and args.precision != 'fp32':
+                    # the same fractions against what the probe measured on THIS box instead of the nominal 2.5 PFLOP/s
+                    delivered = probe['dense']['tflops']
+                    line['roofline']['frac_of_delivered_dense_peak'] = ffn_tflops / delivered
+                    line['end_to_end_frac_of_delivered_dense_peak'] = line['end_to_end_tflops'] / delivered
+            if world == 1 and not args.no_cpu:
+                line['cpu_baseline'] = cpu_baseline(state, args.cpu_seconds)
+                line['speedup_vs_cpu'] = frames_per_s / line['cpu_baseline']['value']
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'ppg': out})
     if args.env_ablation:
         line['ablation_env'] = args.env_ablation
         line['value_under_ablation'] = line['value']
         line['value'] = None
-    return line
+    return line if rank == 0 else None
 
 
 def run_c4(args, rank, world, local_rank, use_dist):
@@ -708,15 +744,30 @@ def run_c4(args, rank, world, local_rank, use_dist):
             block[row, :, frames[mine[j]] * config.HOPSIZE:] = 0.
         padded.append(block)
 
-    def one_pass(keep=False):
+    def one_pass(keep=False, hold=None):
+        """keep: -> the posteriors of every utterance, (frames, 40) per batch.  hold: {batch index: ...} whose entries
+        this pass replaces with those batches' (B, 40, T) outputs (references only: no work is added to the pass)."""
         outs = []
-        for batch, block in zip(batches, padded):
+        for index, (batch, block) in enumerate(zip(batches, padded)):
             lens = [frames[mine[j]] for j in batch]
             mel = ppgs_amd.preprocess.mel.from_audios(block)
             out = model.encode(mel, lens)
             if keep:
                 outs.append(torch.cat([out[row, :, :n].T for row, n in enumerate(lens)], dim=0))
+            if hold is not None and index in hold:
+                hold[index] = out
         return outs
+
+    # --dump-outputs: a fixed, seeded sample of the batches, whose outputs every pass holds on to (from the warm-up on,
+    # so that the timed passes allocate what the warm-up did); the last timed pass's are written after the timed region
+    hold = None
+    if args.dump_outputs and rank == 0:
+        hold, size = {}, 0
+        for index in torch.randperm(len(batches), generator=torch.Generator().manual_seed(0)).tolist():
+            batch_bytes = 40 * 4 * sum(frames[mine[j]] for j in batches[index])
+            if size + batch_bytes > DUMP_SAMPLE_BYTES:
+                continue
+            hold[index], size = None, size + batch_bytes
 
     nccl = use_dist and dist.get_backend() == 'nccl'
 
@@ -727,52 +778,45 @@ def run_c4(args, rank, world, local_rank, use_dist):
             torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        one_pass()
-    model.profile(True, classes=['ffn'], stride=1)
+        one_pass(hold=hold)
+    if args.full:
+        model.profile(True, classes=['ffn'], stride=1)
     barrier()
     start = time.perf_counter()
     for _ in range(args.steps):
-        one_pass()
+        one_pass(hold=hold)
     barrier()
     elapsed = time.perf_counter() - start
-    ffn_ms, ffn_launches = model.profile_read()['ffn']
-    model.profile(False)
+    if args.full:
+        ffn_ms, ffn_launches = model.profile_read()['ffn']
+        model.profile(False)
     if use_dist:
         worst = torch.tensor([elapsed], device='cuda' if nccl else 'cpu', dtype=torch.float64)
         dist.all_reduce(worst, op=dist.ReduceOp.MAX)
         elapsed = float(worst.item())
-    # the only collective of the path: gatherv of the posteriors to rank 0
-    outs = one_pass(keep=True)
-    local = torch.cat(outs, dim=0) if outs else torch.zeros((0, 40), device=DEVICE)
-    order = [mine[j] for batch in batches for j in batch]
-    barrier()
-    start = time.perf_counter()
-    gathered = distributed.gather_ragged(local, [frames[i] for i in order])
-    barrier()
-    gather_ms = 1e3 * (time.perf_counter() - start)
+    if hold is not None:
+        held = sorted(hold)
+        utterances = [mine[j] for index in held for j in batches[index]]
+        dump_outputs(args.dump_outputs, {
+            'ppg_sample': torch.cat([hold[index][row, :, :frames[mine[j]]] for index in held
+                                     for row, j in enumerate(batches[index])], dim=1),
+            'ppg_sample_utterances': torch.tensor(utterances, dtype=torch.float64),
+            'ppg_sample_frames': torch.tensor([frames[i] for i in utterances], dtype=torch.float64)})
+    if args.full:
+        # the only collective of the path: gatherv of the posteriors to rank 0
+        outs = one_pass(keep=True)
+        local = torch.cat(outs, dim=0) if outs else torch.zeros((0, 40), device=DEVICE)
+        order = [mine[j] for batch in batches for j in batch]
+        barrier()
+        start = time.perf_counter()
+        gathered = distributed.gather_ragged(local, [frames[i] for i in order])
+        barrier()
+        gather_ms = 1e3 * (time.perf_counter() - start)
     if rank != 0:
         return None
-    assert sum(len(g) for g in gathered) == args.utterances
     total_frames = sum(frames)
-    # FLOPs of my own shard's launches (rank 0's) for the roofline of its layer kernel
-    processed = 0
-    chip_share = 0.0                 # sum over batches of frames / pipelines: a launch of a p-pipeline batch holds 1/p of the CUs
-    for batch in batches:
-        lens = [frames[mine[j]] for j in batch]
-        _, info = E.plan_windows(len(batch), max(lens), lens)
-        processed += info.processed_frames
-        chip_share += info.processed_frames / model.pipelines(info.tokens)
-    per_frame = 4.0 * HIDDEN * FFN + 2.0 * HIDDEN * HIDDEN + 6.0 * HIDDEN * HIDDEN * (LAYERS - 1) / LAYERS
-    # plain whole-chip accounting: the layer FLOPs of the pass over the SUM of the layer launches' durations (HIP events,
-    # both pipelines' streams), every launch priced against the whole chip -- a launch of a two-pipeline batch shares
-    # the chip with the other pipeline's kernels, so this is a lower bound; the chip-share weighting (a launch of a
-    # p-pipeline batch holds 1/p of the CUs) is kept beside it as frac_of_occupied_cus
-    ffn_tflops = per_frame * processed * LAYERS * args.steps / (1e-3 * ffn_ms) / 1e12 if ffn_ms else 0.0
-    chip_ms = ffn_ms * chip_share / max(processed, 1)
-    occupied_tflops = per_frame * processed * LAYERS * args.steps / (1e-3 * chip_ms) / 1e12 if ffn_ms else 0.0
-    peak = PEAK_FP32_TFLOPS if args.precision == 'fp32' else PEAK_16BIT_TFLOPS
     padded_frames = sum(len(b) * max(frames[mine[j]] for j in b) for b in batches)
-    return {
+    line = {
         'metric': 'PPG frames/sec (whole node), mel repr, 10k ragged utterances packed under max_frames',
         'value': total_frames * args.steps / elapsed,
         'unit': 'frames/s',
@@ -794,6 +838,28 @@ def run_c4(args, rank, world, local_rank, use_dist):
             'rank0_padding_efficiency': sum(frames[i] for i in mine) / max(padded_frames, 1),
             'parallelism': f'utterance-sharded x{world}, gatherv to rank 0 only',
         },
+    }
+    if not args.full:
+        return line
+    assert sum(len(g) for g in gathered) == args.utterances
+    # FLOPs of my own shard's launches (rank 0's) for the roofline of its layer kernel
+    processed = 0
+    chip_share = 0.0                 # sum over batches of frames / pipelines: a launch of a p-pipeline batch holds 1/p of the CUs
+    for batch in batches:
+        lens = [frames[mine[j]] for j in batch]
+        _, info = E.plan_windows(len(batch), max(lens), lens)
+        processed += info.processed_frames
+        chip_share += info.processed_frames / model.pipelines(info.tokens)
+    per_frame = 4.0 * HIDDEN * FFN + 2.0 * HIDDEN * HIDDEN + 6.0 * HIDDEN * HIDDEN * (LAYERS - 1) / LAYERS
+    # plain whole-chip accounting: the layer FLOPs of the pass over the SUM of the layer launches' durations (HIP events,
+    # both pipelines' streams), every launch priced against the whole chip -- a launch of a two-pipeline batch shares
+    # the chip with the other pipeline's kernels, so this is a lower bound; the chip-share weighting (a launch of a
+    # p-pipeline batch holds 1/p of the CUs) is kept beside it as frac_of_occupied_cus
+    ffn_tflops = per_frame * processed * LAYERS * args.steps / (1e-3 * ffn_ms) / 1e12 if ffn_ms else 0.0
+    chip_ms = ffn_ms * chip_share / max(processed, 1)
+    occupied_tflops = per_frame * processed * LAYERS * args.steps / (1e-3 * chip_ms) / 1e12 if ffn_ms else 0.0
+    peak = PEAK_FP32_TFLOPS if args.precision == 'fp32' else PEAK_16BIT_TFLOPS
+    line.update({
         'gather_ms': gather_ms,
         'gather_bytes': total_frames * 40 * 4,
         'roofline': {
@@ -805,7 +871,8 @@ def run_c4(args, rank, world, local_rank, use_dist):
             'chip_share_of_a_launch': chip_share / max(processed, 1),
             'end_to_end_mfma_frac': sum(data.flops(f) for f in frames) * args.steps / elapsed / 1e12 / peak / world,
         },
-    }
+    })
+    return line
 
 
 ###############################################################################

@@ -216,7 +216,7 @@ def _bench_rank(rank, port, world, out_path):
     E.Engine = _StubEngine
     ppgs_amd.preprocess.mel.from_audios = lambda audio: torch.zeros(audio.shape[0], 80, audio.shape[-1] // 160)
     args = argparse.Namespace(gpus=world, steps=1, warmup=1, workload='c4', precision='bf16', utterances=48,
-                              env_config={}, env_ablation={}, no_cpu=True, no_alt=True)
+                              env_config={}, env_ablation={}, no_cpu=True, no_alt=True, full=True, dump_outputs=None)
     if rank == 0:
         with open(out_path, 'w') as f, contextlib.redirect_stdout(f):
             bench.rank_main(args)
@@ -238,3 +238,66 @@ def test_bench_rank_main_c4_two_ranks_over_gloo(tmp_path):
     frames = torch.randint(50, 3001, (48,), generator=generator).tolist()
     assert line['gather_bytes'] == sum(frames) * 40 * 4
     assert line['roofline']['timed_launches'] > 0 and 'rank0_cpus' in line
+
+
+class _MarkingEngine(_StubEngine):
+    """The stub engine with outputs that tell a row's valid frames from its padding (n where valid, -1 beyond)."""
+    calls = 0
+
+    def encode(self, mel, lengths):
+        _MarkingEngine.calls += 1
+        out = torch.full((mel.shape[0], 40, mel.shape[2]), -1.0)
+        for row, n in enumerate(lengths):
+            out[row, :, :n] = float(n)
+        return out
+
+
+def test_bench_plain_c4_runs_k_steps_and_dumps_its_outputs(monkeypatch, tmp_path, capsys):
+    """A plain bench.py run (no --full), one rank, `--workload c4 --steps 3 --warmup 1 --dump-outputs DIR`, with a stub
+    engine on CPU tensors: exactly W + K passes over the batches, a line with the headline fields and none of --full's,
+    and DIR holding the float32 posteriors of a seeded sample of the batches -- only the utterances' valid frames, within
+    the size bound -- which a second run with the same arguments dumps again bit for bit."""
+    import json
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    monkeypatch.syspath_prepend(root)
+    import bench
+    import ppgs_amd
+    from ppgs_amd import engine as E
+    for key in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'PPGS_BENCH_FORCE_DIST'):
+        monkeypatch.delenv(key, raising=False)
+    monkeypatch.setattr(bench, 'DEVICE', 'cpu')
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE_BYTES', 40 * 4 * 40000)
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: True)
+    monkeypatch.setattr(torch.cuda, 'device_count', lambda: 1)
+    monkeypatch.setattr(torch.cuda, 'set_device', lambda device: None)
+    monkeypatch.setattr(torch.cuda, 'synchronize', lambda *a: None)
+    monkeypatch.setattr(ppgs_amd.data, 'row_budget', lambda max_frames, tile_rows=160, gpu=None: None)
+    monkeypatch.setattr(E, 'Engine', _MarkingEngine)
+    monkeypatch.setattr(ppgs_amd.preprocess.mel, 'from_audios',
+                        lambda audio: torch.zeros(audio.shape[0], 80, audio.shape[-1] // 160))
+    dumps = []
+    for run in range(2):
+        args = bench.parse(['--workload', 'c4', '--utterances', '48', '--steps', '3', '--warmup', '1',
+                            '--dump-outputs', str(tmp_path / f'run{run}')])
+        args.env_config, args.env_ablation = bench.env_guard(args)
+        _MarkingEngine.calls = 0
+        bench.rank_main(args)
+        line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        assert _MarkingEngine.calls == (1 + 3) * line['config']['rank0_batches']
+        assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0
+        assert line['unit'] == 'frames/s' and line['higher_is_better'] is True and line['dtype'] == 'bf16'
+        assert 'roofline' not in line and 'gather_ms' not in line
+        dumps.append({name: np.load(tmp_path / f'run{run}' / f'{name}.npy')
+                      for name in ('ppg_sample', 'ppg_sample_utterances', 'ppg_sample_frames')})
+    first, second = dumps
+    ppg, frames = first['ppg_sample'], first['ppg_sample_frames']
+    assert ppg.dtype == np.float32 and frames.dtype == np.float64 and ppg.shape == (40, int(frames.sum()))
+    assert 0 < len(frames) < 48 and ppg.nbytes <= bench.DUMP_SAMPLE_BYTES
+    assert np.array_equal(ppg[0], np.repeat(frames, frames.astype(int)).astype(np.float32))
+    generator = torch.Generator().manual_seed(1234)
+    corpus = torch.randint(50, 3001, (48,), generator=generator).tolist()
+    assert frames.tolist() == [corpus[int(i)] for i in first['ppg_sample_utterances']]
+    for name in first:
+        assert np.array_equal(first[name], second[name])
+    sys.modules.pop('bench', None)

@@ -23,11 +23,11 @@ round=$(echo $tag | sed 's/^\(r[0-9]*\).*/\1/')
 cp $out/${tag}_pmc_summary.txt profiles/${round}_pmc_summary.txt
 cp $out/${tag}_pmc_summary_fp16x2.txt profiles/${round}_pmc_summary_fp16x2.txt
 # the driver's command first (a fresh process, 20 steps), then the default line
-timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver.log 2>&1; grep "^{" $out/bench_driver.log | tail -1 > $out/${tag}_bench.json
-timeout 400 python bench.py > $out/bench_default.log 2>&1; grep "^{" $out/bench_default.log | tail -1 > $out/${tag}_bench_1000steps.json
-PPGS_AMD_STREAMS=1 timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-alt > $out/bench_one.log 2>&1; grep "^{" $out/bench_one.log | tail -1 > $out/${tag}_one_pipeline_bench.json
-timeout 300 python bench.py --precision fp32 --no-alt --no-cpu --steps 20 --warmup 5 > $out/bench_fp32.log 2>&1; grep "^{" $out/bench_fp32.log | tail -1 > $out/${tag}_bench_fp32.json
-timeout 300 python bench.py --precision fp16x2 --no-alt --no-cpu --steps 20 --warmup 5 > $out/bench_x2.log 2>&1; grep "^{" $out/bench_x2.log | tail -1 > $out/${tag}_bench_fp16x2.json
+timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver.log 2>&1; grep "^{" $out/bench_driver.log | tail -1 > $out/${tag}_bench.json
+timeout 400 python bench.py --full > $out/bench_default.log 2>&1; grep "^{" $out/bench_default.log | tail -1 > $out/${tag}_bench_1000steps.json
+PPGS_AMD_STREAMS=1 timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-alt > $out/bench_one.log 2>&1; grep "^{" $out/bench_one.log | tail -1 > $out/${tag}_one_pipeline_bench.json
+timeout 300 python bench.py --full --precision fp32 --no-alt --no-cpu --steps 20 --warmup 5 > $out/bench_fp32.log 2>&1; grep "^{" $out/bench_fp32.log | tail -1 > $out/${tag}_bench_fp32.json
+timeout 300 python bench.py --full --precision fp16x2 --no-alt --no-cpu --steps 20 --warmup 5 > $out/bench_x2.log 2>&1; grep "^{" $out/bench_x2.log | tail -1 > $out/${tag}_bench_fp16x2.json
 # one pipeline under the profiler: the per-kernel whole-chip figures
 ( cd /tmp && export TMPDIR=/tmp && PPGS_AMD_STREAMS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof_${tag}_one/trace -o bench -- python $GRAFT_REPO_ROOT/bench.py --no-cpu --no-alt --steps 20 --warmup 5 > $GRAFT_REPO_ROOT/$out/prof_one.log 2>&1 )
 find gpurun_out/prof_${tag}_one/trace -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/${tag}_one_pipeline_kernel_stats.csv
@@ -37,10 +37,10 @@ timeout 600 bash tests/prof_body.sh $tag > $out/prof_body.log 2>&1
 for n in one two; do cp gpurun_out/prof_${tag}_body/by_grid_${n}_pipelines.txt $out/${tag}_body_by_grid_${n}_pipelines.txt; done
 timeout 600 python tools/bench_c3.py > $out/c3.log 2>&1; grep "^{" $out/c3.log | tail -1 > $out/${tag}_bench_c3.json
 timeout 600 python tools/bench_c3.py fp16x2 > $out/c3_x2.log 2>&1; grep "^{" $out/c3_x2.log | tail -1 > $out/${tag}_bench_c3_fp16x2.json
-PPGS_BENCH_FORCE_DIST=1 timeout 600 python bench.py --workload c4 > $out/c4.log 2>&1; grep "^{" $out/c4.log | tail -1 > $out/${tag}_bench_c4.json
+PPGS_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --workload c4 > $out/c4.log 2>&1; grep "^{" $out/c4.log | tail -1 > $out/${tag}_bench_c4.json
 timeout 300 python tools/bench_streaming.py > $out/c5.log 2>&1; grep "^{" $out/c5.log | tail -1 > $out/${tag}_bench_c5.json
 # the N-rank host path on the one GPU present (gloo; NOT a multi-GPU measurement): 8 launch loops through one GPU's queues
-PPGS_BENCH_ALIAS_GPUS=1 timeout 600 python bench.py --gpus 8 --steps 20 --warmup 5 --no-cpu --no-alt > $out/alias8.log 2>&1; grep "^{" $out/alias8.log | tail -1 > $out/${tag}_bench_alias8_dry_run.json
+PPGS_BENCH_ALIAS_GPUS=1 timeout 600 python bench.py --full --gpus 8 --steps 20 --warmup 5 --no-cpu --no-alt > $out/alias8.log 2>&1; grep "^{" $out/alias8.log | tail -1 > $out/${tag}_bench_alias8_dry_run.json
 timeout 120 python tools/time_frontend.py > $out/time_frontend.txt 2>&1
 # the step as a timeline: which kernels of the two pipelines overlap, where a queue idles (the profiler's own per-dispatch cost included)
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof_${tag}_tl -o bench -- python $GRAFT_REPO_ROOT/bench.py --no-cpu --no-alt --steps 20 --warmup 5 --prewarm-s 0.2 > $GRAFT_REPO_ROOT/$out/prof_tl.log 2>&1 )
