@@ -8,7 +8,6 @@
 #include <string.h>
 
 #include <limits.h>
-#include <array>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -34,6 +33,12 @@ int fail(int code, const char* fmt, ...) {
         hipError_t e_ = (expr);                                                   \
         if (e_ != hipSuccess)                                                     \
             return fail(PPG_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+#define LAUNCH_OK(expr, what)                                                        \
+    do {                                                                             \
+        hipError_t he_ = (expr);                                                     \
+        if (he_ != hipSuccess) return fail(PPG_EDEVICE, "%s: %s", what, hipGetErrorString(he_)); \
     } while (0)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -300,7 +305,6 @@ struct PpgEngine {
     std::vector<hipStream_t> side_streams;
     bool stream_one_pass = false; // PPGS_AMD_STREAM_ONE_PASS=1: KV-cached streams run the split-hidden FFN's reduce + LayerNorm inside the FFN launch (last workgroup of a tile by ticket) -- measured slower: its 64 rows are 4 dependent round trips on 4 waves, 43 us against 18 + 18..30
     int stream_min_rows = 128; // PPGS_AMD_STREAMS_MIN_ROWS: token rows per CU from which a batch is split into pipelines
-    int stream_offset_us = 0;  // PPGS_AMD_STREAM_OFFSET_US: pipeline i of a split batch starts i * this late
     hipEvent_t ev_fork = nullptr;
     std::vector<hipEvent_t> ev_join;
     int l32_debug = 0, h32_debug = 0;         // PPGS_AMD_L32_DEBUG / PPGS_AMD_H32_DEBUG: phase-skipping switches of the timing experiments (wrong results), read once
@@ -530,14 +534,6 @@ void choose_ffn_tiling(const PpgEngine* e, int M, int* nt_out, int* splits_out) 
     *splits_out = splits;
 }
 
-// One wave that holds its stream for `ticks` of the 100 MHz real-time counter: the phase offset between the two
-// pipelines of a split batch (PPGS_AMD_STREAM_OFFSET_US) -- every workgroup of a layer kernel reads its inputs at the
-// launch's start and writes Q / K / V at its end, so two pipelines in phase hit the memory system together.
-__global__ void phase_delay_kernel(unsigned long long ticks) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-}
-
 Workspace layout(const PpgEngine* e, int tokens, int vt_tokens) {
     Workspace w{};
     const size_t M = tokens;
@@ -715,10 +711,35 @@ int get_plan(PpgEngine* e, int batch, int frames, const int64_t* lengths, int le
     return PPG_OK;
 }
 
+// `body` with `n` side streams forked from `s`: each side stream first waits for the work queued on `s` so far, and `s`
+// waits for every side stream's work on every exit -- after an error of `body` too (best effort: the body's error is
+// what is returned), so that the caller's stream always orders after the work queued on the side streams.
+template <class Body>
+int fork_join(hipStream_t s, hipEvent_t fork, const hipStream_t* side, const hipEvent_t* join, size_t n, Body&& body) {
+    if (n == 0) return body();
+    const int rc = [&]() -> int {
+        HIP_OK(hipEventRecord(fork, s));
+        for (size_t i = 0; i < n; ++i) HIP_OK(hipStreamWaitEvent(side[i], fork, 0));
+        return body();
+    }();
+    if (rc != PPG_OK) {
+        for (size_t i = 0; i < n; ++i) {
+            (void)hipEventRecord(join[i], side[i]);
+            (void)hipStreamWaitEvent(s, join[i], 0);
+        }
+        return rc;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        HIP_OK(hipEventRecord(join[i], side[i]));
+        HIP_OK(hipStreamWaitEvent(s, join[i], 0));
+    }
+    return PPG_OK;
+}
+
 struct Timed {
     PpgEngine* e; int cls; hipStream_t s; EventPair ev{}; bool on = false;
-    Timed(PpgEngine* e_, int cls_, hipStream_t s_, bool live = true) : e(e_), cls(cls_), s(s_) {
-        if (!live || !(e->profiling & (1u << cls))) return;
+    Timed(PpgEngine* e_, int cls_, hipStream_t s_) : e(e_), cls(cls_), s(s_) {
+        if (!(e->profiling & (1u << cls))) return;
         if (e->launch_seq[cls]++ % (size_t)e->profile_stride) return;
         auto& pool = e->events[cls];
         size_t& used = e->events_used[cls];
@@ -954,7 +975,6 @@ int ppg_engine_create(const PpgConfig* cfg, const PpgWeights* wts, int device, P
     e->num_streams = std::max(1, std::min(env_switch("PPGS_AMD_STREAMS", e->num_streams), 4));
     e->stream_one_pass = env_experiment("PPGS_AMD_STREAM_ONE_PASS", e->stream_one_pass) != 0;
     e->stream_min_rows = std::max(1, env_experiment("PPGS_AMD_STREAMS_MIN_ROWS", e->stream_min_rows));
-    e->stream_offset_us = std::max(0, env_experiment("PPGS_AMD_STREAM_OFFSET_US", e->stream_offset_us));
     HIP_OK(hipEventCreateWithFlags(&e->ev_fork, kForkJoinEventFlags));
     for (int i = 1; i < e->num_streams; ++i) {
         hipStream_t st;
@@ -1299,234 +1319,240 @@ int ppg_encode(PpgEngine* e, const void* features, int feature_dtype, const int6
         return fail(PPG_EWORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, plan.info.workspace_bytes);
     if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(PPG_EINVAL, "workspace not 256-byte aligned");
 
-    // (a launch outside the segment a call of run_group is asked for is skipped: see `live` there)
-#define LAUNCH_OK(expr, what)                                                        \
-    do {                                                                             \
-        if (live) {                                                                  \
-            hipError_t he_ = (expr);                                                 \
-            if (he_ != hipSuccess) return fail(PPG_EDEVICE, "%s: %s", what, hipGetErrorString(he_)); \
-        }                                                                            \
-    } while (0)
+    // One independent pipeline per plan group, each on its own stream.  A group's route -- its workspace, its tilings,
+    // the kernel form of every layer -- is decided once per call; its launch sequence comes in SEGMENTS -- 0: the head
+    // (gather, input convolution, layer 0's Q/K/V), 1 + l: layer l, 1 + layers: the output convolution -- and every
+    // segment is enqueued once, by the function of its kind below.
+    enum Form { kLayer32, kFfn32x2, kFfnFused, kFfnUnfused };
+    struct Route {
+        const PlanGroup* grp;
+        hipStream_t s;
+        Workspace ws;
+        char *base, *xw, *qk, *vt, *ao, *hid, *Xb;
+        float* X;
+        const char* act_x;
+        int lnt, lnt_ln;
+        bool use32, sub32, head, fuse_op;
+        Form form[PPG_MAX_LAYERS];
+        bool qkv_done[PPG_MAX_LAYERS + 1];   // layer l's Q/K/V came out of the launch before it (layer 0's: out of the head kernel)
+    };
+    auto route_of = [&](const PlanGroup& grp, hipStream_t gs) {
+        Route r{};
+        r.grp = &grp; r.s = gs;
+        const int M = grp.tokens;
+        r.ws = layout(e, grp.tokens, grp.vt_tokens);
+        r.base = static_cast<char*>(workspace) + grp.ws_offset;
+        r.xw = r.base + r.ws.xw;
+        r.X = reinterpret_cast<float*>(r.base + r.ws.x);
+        r.Xb = (e->sz == 2 || e->split) ? r.base + r.ws.xb : nullptr;
+        r.qk = r.base + r.ws.qk;
+        r.vt = r.base + r.ws.vt;
+        r.ao = r.base + r.ws.ao;
+        r.hid = r.base + r.ws.hid;
+        r.act_x = (e->sz == 2 || e->split) ? r.Xb : reinterpret_cast<const char*>(r.X);
 
-    // one independent pipeline per plan group, each on its own stream.  The launch sequence of a group comes in SEGMENTS
-    // -- 0: the head (gather, input convolution, layer 0's Q/K/V), 1 + l: layer l, 1 + layers: the output convolution --
-    // and a call enqueues one of them (seg < 0: all): the groups' segments are enqueued alternately below.
-    const int nseg = c.num_layers + 2;
-    auto run_group = [&](const PlanGroup& grp, hipStream_t s, const int seg) -> int {
-    bool live = seg < 0 || seg == 0;
-    const int M = grp.tokens;
-    const Workspace ws = layout(e, grp.tokens, grp.vt_tokens);
-    char* base = static_cast<char*>(workspace) + grp.ws_offset;
-    char* xw = base + ws.xw;
-    float* X = reinterpret_cast<float*>(base + ws.x);
-    char* Xb = (e->sz == 2 || e->split) ? base + ws.xb : nullptr;
-    char* qk = base + ws.qk;
-    char* vt = base + ws.vt;
-    char* ao = base + ws.ao;
-    char* hid = base + ws.hid;
-    const char* act_x = (e->sz == 2 || e->split) ? Xb : reinterpret_cast<const char*>(X);
+        const int nt = choose_nt(e, M, e->sz == 2 ? 3 : 2);     // linear / conv kernels
+        // linear / conv kernels: measured best at C2 (two 256-register workgroups
+        // per CU): 32-token waves for the wide projections, 16-token waves where
+        // the epilogue dominates (LayerNorm, softmax scatter)
+        const bool forced = e->lin_nt >= 1 && e->lin_nt <= 3;
+        r.lnt = forced ? e->lin_nt : std::min(nt, 2);
+        r.lnt_ln = forced ? e->lin_nt : 1;
 
-    const int nt = choose_nt(e, M, e->sz == 2 ? 3 : 2);     // linear / conv kernels
-    // linear / conv kernels: measured best at C2 (two 256-register workgroups
-    // per CU): 32-token waves for the wide projections, 16-token waves where
-    // the epilogue dominates (LayerNorm, softmax scatter)
-    const bool forced = e->lin_nt >= 1 && e->lin_nt <= 3;
-    const int lnt = forced ? e->lin_nt : std::min(nt, 2);
-    const int lnt_ln = forced ? e->lin_nt : 1;
-
-    const bool use32 = e->layer32 && e->ffn_fused && ws.ffn_splits == 1;
-    // (one 160-token tile per workgroup: below half a chip of tiles the three launches, with their smaller workgroups, are as fast)
-    const int tiles32 = (M + ppg::layer32_tokens(H) - 1) / ppg::layer32_tokens(H);
-    // sub-tile workgroups (two token blocks, three per tile) when whole tiles would leave two thirds of the CUs idle
-    const bool sub32 = use32 && e->subtile && H == 256 && (F / 128) % 2 == 0 && 3 * tiles32 <= e->num_cus;
-    const bool head = use32 && e->head32 && (2 * tiles32 >= e->num_cus || sub32);
-    if (head) {
-        Timed t(e, PPG_K_INCONV, s, live);
-        Head32Args a{};
-        a.feats = features; a.dtype = feature_dtype; a.C = c.input_channels; a.T = frames; a.overlap = c.chunk_overlap;
-        a.win_img = e->win_img; a.b_in = e->b_in; a.pe = e->pe; a.X = X;
-        a.wq_img = e->layers[0].wq_img; a.bq = e->layers[0].bqkv; a.qk_out = qk; a.vt_out = vt; a.vt_ld = ws.vt_ld;
-        a.blk_win = grp.d_blk; a.win = grp.d_win; a.M = M; a.H = H;
-        a.tiles = (M + ppg::layer32_tokens(H) - 1) / ppg::layer32_tokens(H);
-        a.nwin = (int)grp.windows.size(); a.vt_rows = H; a.vt_tokens = grp.vt_tokens;
-        a.qk_slack = qk + (size_t)M * 2 * H * e->sz; a.qk_slack_bytes = (int)(64 * 2 * H * e->sz);
-        a.debug_mode = e->h32_debug;
-        a.x_half = e->x16;
-        a.sub_tiles = sub32;
-        a.dbg = e->head_dbg;
-        LAUNCH_OK(ppg::launch_head32(prec, a, s), "head32");
-    }
-    if (!head) {
-        Timed t(e, PPG_K_GATHER, s, live);
-        GatherArgs g{};
-        g.feats = features; g.dtype = feature_dtype; g.C = c.input_channels; g.T = frames;
-        g.overlap = c.chunk_overlap; g.xw = xw; g.Cp = e->Cp;
-        g.blk_win = grp.d_blk; g.win = grp.d_win; g.M = M;
-        // V^T padding columns and the K rows past the last token are read (masked)
-        // by the attention tiles: the same launch keeps them finite
-        g.vt = vt; g.vt_ld = ws.vt_ld; g.vt_rows = H; g.vt_tokens = grp.vt_tokens; g.nwin = (int)grp.windows.size();
-        g.qk_slack = qk + (size_t)M * 2 * H * e->sz; g.qk_slack_bytes = (int)(64 * 2 * H * e->sz);
-        LAUNCH_OK(ppg::launch_gather(prec, g, s), "gather");
-    }
-    auto base_args = [&]() {
+        r.use32 = e->layer32 && e->ffn_fused && r.ws.ffn_splits == 1;
+        // (one 160-token tile per workgroup: below half a chip of tiles the three launches, with their smaller workgroups, are as fast)
+        const int tiles32 = (M + ppg::layer32_tokens(H) - 1) / ppg::layer32_tokens(H);
+        // sub-tile workgroups (two token blocks, three per tile) when whole tiles would leave two thirds of the CUs idle
+        r.sub32 = r.use32 && e->subtile && H == 256 && (F / 128) % 2 == 0 && 3 * tiles32 <= e->num_cus;
+        r.head = r.use32 && e->head32 && (2 * tiles32 >= e->num_cus || r.sub32);
+        r.fuse_op = e->ffn_fused && e->op_fused && r.ws.ffn_splits == 1;
+        r.qkv_done[0] = r.head;
+        for (int l = 0; l < c.num_layers; ++l) {
+            const bool more = l + 1 < c.num_layers;
+            const bool x2_layer = e->split && e->ffn32x2 > 0 && e->layers[l].w1x_img && 2 * ((M + ppg::ffn32x2_tokens() - 1) / ppg::ffn32x2_tokens()) >= e->num_cus;
+            if (r.use32) { r.form[l] = kLayer32; r.qkv_done[l + 1] = e->qkv_fused && more; }
+            else if (x2_layer) { r.form[l] = kFfn32x2; r.qkv_done[l + 1] = e->ffn32x2 >= 3 && more; }
+            else if (e->ffn_fused) { r.form[l] = kFfnFused; r.qkv_done[l + 1] = r.fuse_op && e->qkv_fused && more; }
+            else { r.form[l] = kFfnUnfused; r.qkv_done[l + 1] = false; }
+        }
+        return r;
+    };
+    auto base_args = [&](const Route& r) {
         LinearArgs a{};
-        a.blk_win = grp.d_blk; a.win = grp.d_win; a.M = M; a.H = H;
-        a.X = X; a.Xb = Xb; a.v_start = INT_MAX; a.taps = 1;
+        a.blk_win = r.grp->d_blk; a.win = r.grp->d_win; a.M = r.grp->tokens; a.H = H;
+        a.X = r.X; a.Xb = r.Xb; a.v_start = INT_MAX; a.taps = 1;
         return a;
     };
-    if (!head) {
-        Timed t(e, PPG_K_INCONV, s, live);
-        LinearArgs a = base_args();
-        a.x_tiled = use32 ? (e->x16 ? 2 : 1) : 0;
-        a.act = xw; a.lda_bytes = e->Cp * e->sz; a.taps = 5;
+    const int hg = H / e->KG;   // K-groups of a hidden-wide row
+
+    auto enqueue_head = [&](const Route& r) -> int {
+        const PlanGroup& grp = *r.grp;
+        const int M = grp.tokens;
+        if (r.head) {
+            Timed t(e, PPG_K_INCONV, r.s);
+            Head32Args a{};
+            a.feats = features; a.dtype = feature_dtype; a.C = c.input_channels; a.T = frames; a.overlap = c.chunk_overlap;
+            a.win_img = e->win_img; a.b_in = e->b_in; a.pe = e->pe; a.X = r.X;
+            a.wq_img = e->layers[0].wq_img; a.bq = e->layers[0].bqkv; a.qk_out = r.qk; a.vt_out = r.vt; a.vt_ld = r.ws.vt_ld;
+            a.blk_win = grp.d_blk; a.win = grp.d_win; a.M = M; a.H = H;
+            a.tiles = (M + ppg::layer32_tokens(H) - 1) / ppg::layer32_tokens(H);
+            a.nwin = (int)grp.windows.size(); a.vt_rows = H; a.vt_tokens = grp.vt_tokens;
+            a.qk_slack = r.qk + (size_t)M * 2 * H * e->sz; a.qk_slack_bytes = (int)(64 * 2 * H * e->sz);
+            a.debug_mode = e->h32_debug;
+            a.x_half = e->x16;
+            a.sub_tiles = r.sub32;
+            a.dbg = e->head_dbg;
+            LAUNCH_OK(ppg::launch_head32(prec, a, r.s), "head32");
+            return PPG_OK;
+        }
+        {
+            Timed t(e, PPG_K_GATHER, r.s);
+            GatherArgs g{};
+            g.feats = features; g.dtype = feature_dtype; g.C = c.input_channels; g.T = frames;
+            g.overlap = c.chunk_overlap; g.xw = r.xw; g.Cp = e->Cp;
+            g.blk_win = grp.d_blk; g.win = grp.d_win; g.M = M;
+            // V^T padding columns and the K rows past the last token are read (masked)
+            // by the attention tiles: the same launch keeps them finite
+            g.vt = r.vt; g.vt_ld = r.ws.vt_ld; g.vt_rows = H; g.vt_tokens = grp.vt_tokens; g.nwin = (int)grp.windows.size();
+            g.qk_slack = r.qk + (size_t)M * 2 * H * e->sz; g.qk_slack_bytes = (int)(64 * 2 * H * e->sz);
+            LAUNCH_OK(ppg::launch_gather(prec, g, r.s), "gather");
+        }
+        Timed t(e, PPG_K_INCONV, r.s);
+        LinearArgs a = base_args(r);
+        a.x_tiled = r.use32 ? (e->x16 ? 2 : 1) : 0;
+        a.act = r.xw; a.lda_bytes = e->Cp * e->sz; a.taps = 5;
         a.groups_per_tap = e->in_groups_per_tap; a.real_groups = 5 * e->in_groups_per_tap;
         a.total_groups = e->in_total_groups;
         a.W = e->w_in; a.bias = e->b_in; a.N = H; a.pe = e->pe;
         if (e->lin_dbg_class == PPG_K_INCONV) a.dbg = e->lin_dbg;
-        LAUNCH_OK(ppg::launch_linear(prec, EPI_INCONV, 16, lnt, a, H / 256, s), "in-conv");
-    }
-    const int hg = H / e->KG;   // K-groups of a hidden-wide row
-    bool qkv_done = head;    // this layer's Q/K/V came out of the previous layer's FFN kernel (layer 0's: out of the head kernel)
-    for (int l = 0; l < c.num_layers; ++l) {
+        LAUNCH_OK(ppg::launch_linear(prec, EPI_INCONV, 16, r.lnt, a, H / 256, r.s), "in-conv");
+        return PPG_OK;
+    };
+
+    auto enqueue_layer = [&](const Route& r, int l) -> int {
+        const PlanGroup& grp = *r.grp;
+        const int M = grp.tokens;
         const DevLayer& d = e->layers[l];
-        live = seg < 0 || seg == 1 + l;
-        if (!qkv_done) {
-            Timed t(e, PPG_K_QKV, s, live);
-            LinearArgs a = base_args();
-            a.act = act_x; a.lda_bytes = H * e->sz;
+        const bool qkv_next = r.qkv_done[l + 1];   // this launch computes the next layer's Q/K/V as its tail
+        if (!r.qkv_done[l]) {
+            Timed t(e, PPG_K_QKV, r.s);
+            LinearArgs a = base_args(r);
+            a.act = r.act_x; a.lda_bytes = H * e->sz;
             a.groups_per_tap = hg; a.real_groups = hg; a.total_groups = hg;
             a.W = d.wqkv; a.bias = d.bqkv; a.N = 3 * H;
-            a.out_rows = qk; a.out_ld = 2 * H; a.vt = vt; a.vt_ld = ws.vt_ld; a.v_start = 2 * H;
+            a.out_rows = r.qk; a.out_ld = 2 * H; a.vt = r.vt; a.vt_ld = r.ws.vt_ld; a.v_start = 2 * H;
             if (l == 0 && e->lin_dbg_class == PPG_K_QKV) a.dbg = e->lin_dbg;
-            LAUNCH_OK(ppg::launch_linear(prec, EPI_QKV, 16, lnt, a, 3 * H / 256, s), "qkv");
+            LAUNCH_OK(ppg::launch_linear(prec, EPI_QKV, 16, r.lnt, a, 3 * H / 256, r.s), "qkv");
         }
         {
-            Timed t(e, PPG_K_ATTENTION, s, live);
+            Timed t(e, PPG_K_ATTENTION, r.s);
             AttnArgs a{};
-            a.qk = qk; a.qk_ld_bytes = 2 * H * e->sz; a.vt = vt; a.vt_ld_bytes = ws.vt_ld * e->sz;
-            a.ao = ao; a.H = H; a.causal = c.is_causal;
-            a.items = grp.d_items; a.win = grp.d_win; a.M = M; a.ao_tiled = use32; a.heads = c.heads;
+            a.qk = r.qk; a.qk_ld_bytes = 2 * H * e->sz; a.vt = r.vt; a.vt_ld_bytes = r.ws.vt_ld * e->sz;
+            a.ao = r.ao; a.H = H; a.causal = c.is_causal;
+            a.items = grp.d_items; a.win = grp.d_win; a.M = M; a.ao_tiled = r.use32; a.heads = c.heads;
             a.dbg = l == 0 ? e->attn_dbg : nullptr;
-            LAUNCH_OK(ppg::launch_attn(prec, a, (int)grp.items.size(), c.heads, e->head_dim, s), "attention");
+            LAUNCH_OK(ppg::launch_attn(prec, a, (int)grp.items.size(), c.heads, e->head_dim, r.s), "attention");
         }
-        if (use32) {
-            Timed t(e, PPG_K_FFN, s, live);
+        if (r.form[l] == kLayer32) {
+            Timed t(e, PPG_K_FFN, r.s);
             Layer32Args a{};
-            a.ao = ao; a.wo_img = d.wo_img; a.w1_img = d.w1_img; a.w2_img = d.w2_img;
+            a.ao = r.ao; a.wo_img = d.wo_img; a.w1_img = d.w1_img; a.w2_img = d.w2_img;
             a.bo = d.bo; a.g1 = d.g1; a.e1 = d.e1; a.b1 = d.b1; a.b2 = d.b2; a.g2 = d.g2; a.e2 = d.e2;
-            a.X = X; a.Xb = Xb; a.M = M; a.F = F; a.H = H; a.dbg = l == 0 ? e->ffn_dbg : nullptr;
+            a.X = r.X; a.Xb = r.Xb; a.M = M; a.F = F; a.H = H; a.dbg = l == 0 ? e->ffn_dbg : nullptr;
             a.debug_mode = e->l32_debug;
             a.x_half = e->x16;
-            a.sub_tiles = sub32;
-                qkv_done = e->qkv_fused && l + 1 < c.num_layers;
+            a.sub_tiles = r.sub32;
             a.write_x = l + 1 < c.num_layers;
-            if (qkv_done) {
+            if (qkv_next) {
                 const DevLayer& nx = e->layers[l + 1];
-                a.wq_img = nx.wq_img; a.bq = nx.bqkv; a.qk_out = qk; a.vt_out = vt; a.vt_ld = ws.vt_ld;
+                a.wq_img = nx.wq_img; a.bq = nx.bqkv; a.qk_out = r.qk; a.vt_out = r.vt; a.vt_ld = r.ws.vt_ld;
                 a.blk_win = grp.d_blk; a.win = grp.d_win;
                 a.Xb = nullptr;              // nobody reads the 16-bit copy: x2 goes straight into the tail
             }
-            LAUNCH_OK(ppg::launch_layer32(prec, a, s), "layer32");
-            continue;
+            LAUNCH_OK(ppg::launch_layer32(prec, a, r.s), "layer32");
+            return PPG_OK;
         }
-        const bool fuse_op = e->ffn_fused && e->op_fused && ws.ffn_splits == 1;
-        const bool x2_layer = e->split && e->ffn32x2 > 0 && d.w1x_img && 2 * ((M + ppg::ffn32x2_tokens() - 1) / ppg::ffn32x2_tokens()) >= e->num_cus;
-        if (!fuse_op && !(x2_layer && e->ffn32x2 >= 2)) {
-            Timed t(e, PPG_K_OUTPROJ_LN, s, live);
-            LinearArgs a = base_args();
-            a.act = ao; a.lda_bytes = H * e->sz;
+        if (!r.fuse_op && !(r.form[l] == kFfn32x2 && e->ffn32x2 >= 2)) {
+            Timed t(e, PPG_K_OUTPROJ_LN, r.s);
+            LinearArgs a = base_args(r);
+            a.act = r.ao; a.lda_bytes = H * e->sz;
             a.groups_per_tap = hg; a.real_groups = hg; a.total_groups = hg;
             a.W = d.wo; a.bias = d.bo; a.N = H; a.gamma = d.g1; a.beta = d.e1;
             if (l == 0 && e->lin_dbg_class == PPG_K_OUTPROJ_LN) a.dbg = e->lin_dbg;
-            LAUNCH_OK(ppg::launch_linear(prec, EPI_RESLN, H / 16, lnt_ln, a, 1, s), "out-proj+LN");
+            LAUNCH_OK(ppg::launch_linear(prec, EPI_RESLN, H / 16, r.lnt_ln, a, 1, r.s), "out-proj+LN");
         }
-        {
-            Timed t(e, PPG_K_FFN, s, live);
-            if (x2_layer) {
-                Ffn32X2Args a{};
-                a.xb = Xb; a.X = X; a.xb_out = Xb; a.w1_img = d.w1x_img; a.w2_img = d.w2x_img;
-                a.b1 = d.b1; a.b2 = d.b2; a.g2 = d.g2; a.e2 = d.e2; a.M = M; a.F = F; a.H = H;
-                if (e->ffn32x2 >= 2) { a.ao = ao; a.wo_img = d.wox_img; a.bo = d.bo; a.g1 = d.g1; a.e1 = d.e1; }
-                a.dbg = l == 0 ? e->ffn_dbg : nullptr;
-                qkv_done = e->ffn32x2 >= 3 && l + 1 < c.num_layers;
-                if (qkv_done) {
-                    const DevLayer& nx = e->layers[l + 1];
-                    a.wq_img = nx.wqx_img; a.bq = nx.bqkv; a.qk_out = qk; a.vt_out = vt; a.vt_ld = ws.vt_ld;
-                    a.blk_win = grp.d_blk; a.win = grp.d_win;
-                }
-                LAUNCH_OK(ppg::launch_ffn32x2(a, s), "ffn32x2");
-            } else if (e->ffn_fused) {
-                FfnArgs a{};
-                a.X = X; a.Xb = Xb; a.W1 = d.w1; a.b1 = d.b1; a.W2p = d.w2p; a.b2 = d.b2;
-                a.gamma = d.g2; a.beta = d.e2; a.H = H; a.F = F; a.M = M; a.dbg = l == 0 ? e->ffn_dbg : nullptr;
-                a.splits = ws.ffn_splits;
-                a.partial = ws.ffn_splits > 1 ? reinterpret_cast<float*>(base + ws.part) : nullptr;
-                if (fuse_op) { a.ao = ao; a.Wo = d.wo; a.bo = d.bo; a.g1 = d.g1; a.e1 = d.e1; a.W1 = d.w1k; }
-                qkv_done = fuse_op && e->qkv_fused && l + 1 < c.num_layers;
-                if (qkv_done) {
-                    const DevLayer& nx = e->layers[l + 1];
-                    a.Wq = nx.wqkvk; a.bq = nx.bqkv; a.qk_out = qk; a.vt_out = vt; a.vt_ld = ws.vt_ld;
-                    a.blk_win = grp.d_blk; a.win = grp.d_win;
-                }
-                LAUNCH_OK(ppg::launch_ffn(prec, a, ws.ffn_nt, s), "ffn");
-            } else {
-                qkv_done = false;
-                LinearArgs a = base_args();
-                a.act = act_x; a.lda_bytes = H * e->sz;
-                a.groups_per_tap = hg; a.real_groups = hg; a.total_groups = hg;
-                a.W = d.w1; a.bias = d.b1; a.N = F; a.out_rows = hid; a.out_ld = F;
-                LAUNCH_OK(ppg::launch_linear(prec, EPI_RELU, 16, lnt, a, F / 256, s), "ffn1");
-                LinearArgs b = base_args();
-                const int fg = F / e->KG;
-                b.act = hid; b.lda_bytes = F * e->sz;
-                b.groups_per_tap = fg; b.real_groups = fg; b.total_groups = fg;
-                b.W = d.w2; b.bias = d.b2; b.N = H; b.gamma = d.g2; b.beta = d.e2;
-                LAUNCH_OK(ppg::launch_linear(prec, EPI_RESLN, H / 16, lnt_ln, b, 1, s), "ffn2+LN");
+        Timed t(e, PPG_K_FFN, r.s);
+        if (r.form[l] == kFfn32x2) {
+            Ffn32X2Args a{};
+            a.xb = r.Xb; a.X = r.X; a.xb_out = r.Xb; a.w1_img = d.w1x_img; a.w2_img = d.w2x_img;
+            a.b1 = d.b1; a.b2 = d.b2; a.g2 = d.g2; a.e2 = d.e2; a.M = M; a.F = F; a.H = H;
+            if (e->ffn32x2 >= 2) { a.ao = r.ao; a.wo_img = d.wox_img; a.bo = d.bo; a.g1 = d.g1; a.e1 = d.e1; }
+            a.dbg = l == 0 ? e->ffn_dbg : nullptr;
+            if (qkv_next) {
+                const DevLayer& nx = e->layers[l + 1];
+                a.wq_img = nx.wqx_img; a.bq = nx.bqkv; a.qk_out = r.qk; a.vt_out = r.vt; a.vt_ld = r.ws.vt_ld;
+                a.blk_win = grp.d_blk; a.win = grp.d_win;
             }
+            LAUNCH_OK(ppg::launch_ffn32x2(a, r.s), "ffn32x2");
+        } else if (r.form[l] == kFfnFused) {
+            FfnArgs a{};
+            a.X = r.X; a.Xb = r.Xb; a.W1 = d.w1; a.b1 = d.b1; a.W2p = d.w2p; a.b2 = d.b2;
+            a.gamma = d.g2; a.beta = d.e2; a.H = H; a.F = F; a.M = M; a.dbg = l == 0 ? e->ffn_dbg : nullptr;
+            a.splits = r.ws.ffn_splits;
+            a.partial = r.ws.ffn_splits > 1 ? reinterpret_cast<float*>(r.base + r.ws.part) : nullptr;
+            if (r.fuse_op) { a.ao = r.ao; a.Wo = d.wo; a.bo = d.bo; a.g1 = d.g1; a.e1 = d.e1; a.W1 = d.w1k; }
+            if (qkv_next) {
+                const DevLayer& nx = e->layers[l + 1];
+                a.Wq = nx.wqkvk; a.bq = nx.bqkv; a.qk_out = r.qk; a.vt_out = r.vt; a.vt_ld = r.ws.vt_ld;
+                a.blk_win = grp.d_blk; a.win = grp.d_win;
+            }
+            LAUNCH_OK(ppg::launch_ffn(prec, a, r.ws.ffn_nt, r.s), "ffn");
+        } else {
+            LinearArgs a = base_args(r);
+            a.act = r.act_x; a.lda_bytes = H * e->sz;
+            a.groups_per_tap = hg; a.real_groups = hg; a.total_groups = hg;
+            a.W = d.w1; a.bias = d.b1; a.N = F; a.out_rows = r.hid; a.out_ld = F;
+            LAUNCH_OK(ppg::launch_linear(prec, EPI_RELU, 16, r.lnt, a, F / 256, r.s), "ffn1");
+            LinearArgs b = base_args(r);
+            const int fg = F / e->KG;
+            b.act = r.hid; b.lda_bytes = F * e->sz;
+            b.groups_per_tap = fg; b.real_groups = fg; b.total_groups = fg;
+            b.W = d.w2; b.bias = d.b2; b.N = H; b.gamma = d.g2; b.beta = d.e2;
+            LAUNCH_OK(ppg::launch_linear(prec, EPI_RESLN, H / 16, r.lnt_ln, b, 1, r.s), "ffn2+LN");
         }
-    }
-    live = seg < 0 || seg == 1 + c.num_layers;
-    {
-        Timed t(e, PPG_K_OUTCONV_SOFTMAX, s, live);
-        LinearArgs a = base_args();
-        a.act = act_x; a.lda_bytes = H * e->sz; a.taps = 5;
+        return PPG_OK;
+    };
+
+    auto enqueue_outconv = [&](const Route& r) -> int {
+        Timed t(e, PPG_K_OUTCONV_SOFTMAX, r.s);
+        LinearArgs a = base_args(r);
+        a.act = r.act_x; a.lda_bytes = H * e->sz; a.taps = 5;
         a.groups_per_tap = e->out_groups_per_tap; a.real_groups = 5 * e->out_groups_per_tap;
         a.total_groups = e->out_total_groups;
         a.W = e->w_out; a.bias = e->b_out; a.N = 48;
         a.out = out; a.out_T = frames; a.out_C = c.output_channels; a.softmax = softmax;
         a.overflow = e->d_overflow;
         if (e->lin_dbg_class == PPG_K_OUTCONV_SOFTMAX) a.dbg = e->lin_dbg;
-        if (e->outconv && ppg::outconv_supported(prec, a)) LAUNCH_OK(ppg::launch_outconv(prec, a, s), "out-conv+softmax");
-        else LAUNCH_OK(ppg::launch_linear(prec, EPI_OUTCONV, 3, lnt_ln, a, 1, s), "out-conv+softmax");
-    }
-    return PPG_OK;
-    };   // run_group
+        if (e->outconv && ppg::outconv_supported(prec, a)) LAUNCH_OK(ppg::launch_outconv(prec, a, r.s), "out-conv+softmax");
+        else LAUNCH_OK(ppg::launch_linear(prec, EPI_OUTCONV, 3, r.lnt_ln, a, 1, r.s), "out-conv+softmax");
+        return PPG_OK;
+    };
 
-    const size_t ngroups = plan.groups.size();
-    if (ngroups > 1) HIP_OK(hipEventRecord(e->ev_fork, s));
-    for (size_t gi = 1; gi < ngroups; ++gi) {
-        hipStream_t side = e->side_streams[gi - 1];
-        HIP_OK(hipStreamWaitEvent(side, e->ev_fork, 0));
-        if (e->stream_offset_us > 0)
-            hipLaunchKernelGGL(phase_delay_kernel, dim3(1), dim3(64), 0, side, (unsigned long long)(100ull * e->stream_offset_us * gi));
-    }
+    std::vector<Route> routes;
+    routes.reserve(plan.groups.size());
+    for (size_t gi = 0; gi < plan.groups.size(); ++gi) routes.push_back(route_of(plan.groups[gi], gi == 0 ? s : e->side_streams[gi - 1]));
     // The pipelines' launches are enqueued segment by segment, alternately: enqueued one whole pipeline after the
     // other, the second one's first kernel reached its queue ~50 us (a dozen launches) behind the first one's -- nothing
     // in a loop of steps, where the host runs ahead of the device, but the first step of a short timed block (and a
     // latency-bound caller's only step) started one pipeline that much late (tools/block_overhead.py).
-    if (ngroups == 1) {
-        if ((rc = run_group(plan.groups[0], s, -1))) return rc;
-    } else {
-        for (int seg = 0; seg < nseg; ++seg)
-            for (size_t gi = 0; gi < ngroups; ++gi)
-                if ((rc = run_group(plan.groups[gi], gi == 0 ? s : e->side_streams[gi - 1], seg))) return rc;
-    }
-    for (size_t gi = 1; gi < ngroups; ++gi) {
-        HIP_OK(hipEventRecord(e->ev_join[gi - 1], e->side_streams[gi - 1]));
-        HIP_OK(hipStreamWaitEvent(s, e->ev_join[gi - 1], 0));
-    }
-#undef LAUNCH_OK
-    return PPG_OK;
+    return fork_join(s, e->ev_fork, e->side_streams.data(), e->ev_join.data(), routes.size() - 1, [&]() -> int {
+        for (int seg = 0; seg < c.num_layers + 2; ++seg)
+            for (const Route& r : routes) {
+                const int rc = seg == 0 ? enqueue_head(r) : seg <= c.num_layers ? enqueue_layer(r, seg - 1) : enqueue_outconv(r);
+                if (rc) return rc;
+            }
+        return PPG_OK;
+    });
 }
 
 // ----------------------------------------------------------------------------
@@ -1592,24 +1618,9 @@ struct PpgStream {
     char* staging = nullptr;
     hipEvent_t uploaded[kSlots] = {};
     unsigned step = 0;
-    // A step's ~22 launches behind the table upload as ONE hipGraph replay (round 5).  The launches of a step are a
-    // function of (row blocks per map, query tiles, softmax): a stream advanced at a steady cadence repeats a handful
-    // of keys.  A key seen for the second time is captured (on the stream's own capture stream: the caller's may be
-    // the legacy null stream, which cannot capture), from then on replayed.  OFF by default (PPGS_AMD_STREAM_GRAPH=1 turns
-    // it on): on ROCm 7.2 the replay of these 22 short nodes plus the fork / join events adds 45 - 50 us to a synchronised
-    // step (one stream 266 -> 315 us, 64 streams 361 -> 406 us): the step is bound by its dependent kernels, not by launches.
-    struct StepGraph { hipGraphExec_t exec = nullptr; int seen = 0; };
-    std::map<std::array<int, 6>, StepGraph> graphs;
-    hipStream_t gstream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool graph_steps = false;     // (measured: a replay costs MORE than the launches it replaces, profiles/r5_stream_step_graph.txt)
     bool fused_layers = false;    // PPGS_AMD_STREAM_FUSED=2 at creation: every step's layers as ONE fused launch each (for streams pushed in whole chunks); fixed for the life of the stream
     ~PpgStream() {
         if (e) (void)hipSetDevice(e->device);
-        for (auto& kv : graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-        if (gstream) (void)hipStreamDestroy(gstream);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
         for (void* p : {(void*)buf, (void*)feats, (void*)probs, (void*)d_blk, (void*)d_tables, (void*)d_tickets}) if (p) (void)hipFree(p);
         if (staging) (void)hipHostFree(staging);
         for (hipEvent_t ev : uploaded) if (ev) (void)hipEventDestroy(ev);
@@ -1628,7 +1639,6 @@ int ppg_stream_create_batch(PpgEngine* e, int batch, int max_frames, int feature
     HIP_OK(hipSetDevice(e->device));
     std::unique_ptr<PpgStream> st(new PpgStream);
     st->e = e; st->batch = batch; st->cap = max_frames; st->rows = round_up(max_frames, 32); st->dtype = feature_dtype;
-    st->graph_steps = ppg::env_experiment("PPGS_AMD_STREAM_GRAPH", 0) != 0;
     st->fused_layers = ppg::env_switch("PPGS_AMD_STREAM_FUSED", 0) == 2;
     st->received.assign(batch, 0); st->x_valid.assign(batch, 0); st->o_valid.assign(batch, 0); st->finished.assign(batch, 0);
     const PpgConfig& c = e->cfg;
@@ -1786,34 +1796,10 @@ int ppg_stream_push_batch(PpgStream* st, const void* chunk, int nmax, const int*
         memcpy(stage + used, maps.data() + (size_t)k * tb.max_blocks, (size_t)padded * sizeof(int));
         used = align_up(used + (size_t)padded * sizeof(int), 64);
     }
-    // the launch stream: the caller's, or (graph mode) the stream's own behind a fork event
-    hipStream_t caller = s;
-    PpgStream::StepGraph* sg = nullptr;
-    if (st->graph_steps) {
-        if (!st->gstream) {
-            HIP_OK(hipStreamCreateWithFlags(&st->gstream, hipStreamNonBlocking));
-            HIP_OK(hipEventCreateWithFlags(&st->ev_fork, hipEventDisableTiming));
-            HIP_OK(hipEventCreateWithFlags(&st->ev_join, hipEventDisableTiming));
-        }
-        if (st->graphs.size() >= 32) {               // (an irregular cadence: start over rather than grow)
-            for (auto& kv : st->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-            st->graphs.clear();
-        }
-        sg = &st->graphs[std::array<int, 6>{nmap[0], nmap[1], nmap[2], nitems, softmax, max_count > 0}];       // (the fused-layer choice follows nmap[0])
-        HIP_OK(hipEventRecord(st->ev_fork, caller));
-        HIP_OK(hipStreamWaitEvent(st->gstream, st->ev_fork, 0));
-        s = st->gstream;
-    }
     HIP_OK(hipMemcpyAsync(st->d_tables, stage, used, hipMemcpyHostToDevice, s));
     const PpgWindow* d_win = reinterpret_cast<const PpgWindow*>(st->d_tables + tb.win);
     const StreamItemMeta* d_meta = reinterpret_cast<const StreamItemMeta*>(st->d_tables + tb.meta);
     const AttnItem* d_items = reinterpret_cast<const AttnItem*>(st->d_tables + tb.items);
-
-#define LAUNCH_OK(expr, what)                                                        \
-    do {                                                                             \
-        hipError_t he_ = (expr);                                                     \
-        if (he_ != hipSuccess) return fail(PPG_EDEVICE, "%s: %s", what, hipGetErrorString(he_)); \
-    } while (0)
 
     if (max_count > 0) {
         const int per_item = c.input_channels * max_count;
@@ -1821,42 +1807,6 @@ int ppg_stream_push_batch(PpgStream* st, const void* chunk, int nmax, const int*
                            d_meta, static_cast<const char*>(chunk), nmax, c.input_channels, R, esz, st->feats);
         LAUNCH_OK(hipGetLastError(), "stream append");
     }
-    // everything from here to the out-convolution depends on the key only: replay it, or capture it on its second
-    // appearance (every kernel of the sequence has then run eagerly once: their one-time attribute calls are done)
-    bool capturing = false;
-    auto finish = [&](int rc) {                       // leave the capture (if any), join the caller's stream
-        if (capturing) {
-            hipGraph_t graph = nullptr;
-            const hipError_t he = hipStreamEndCapture(s, &graph);
-            capturing = false;
-            if (rc == PPG_OK && he == hipSuccess && graph) {
-                if (hipGraphInstantiate(&sg->exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                    if (hipGraphLaunch(sg->exec, s) != hipSuccess) rc = fail(PPG_EDEVICE, "stream step: graph launch failed");
-                } else {
-                    sg->exec = nullptr;
-                    rc = fail(PPG_EDEVICE, "stream step: graph instantiation failed");
-                }
-            } else if (rc == PPG_OK) {
-                rc = fail(PPG_EDEVICE, "stream step: capture failed: %s", hipGetErrorString(he));
-            }
-            if (graph) (void)hipGraphDestroy(graph);
-            if (rc != PPG_OK) sg->seen = -(1 << 30);        // (never try this key again)
-        }
-        return rc;
-    };
-#undef LAUNCH_OK
-#define LAUNCH_OK(expr, what)                                                        \
-    do {                                                                             \
-        hipError_t he_ = (expr);                                                     \
-        if (he_ != hipSuccess) return finish(fail(PPG_EDEVICE, "%s: %s", what, hipGetErrorString(he_))); \
-    } while (0)
-    const bool replay = sg && sg->exec;
-    if (sg && !replay && ++sg->seen >= 2) {
-        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) capturing = true;
-    }
-    if (replay) {
-        if (hipGraphLaunch(sg->exec, s) != hipSuccess) return fail(PPG_EDEVICE, "stream step: graph launch failed");
-    } else {
     char* base = st->buf;
     const Workspace& ws = st->ws;
     char* xw = base + ws.xw;
@@ -1980,14 +1930,7 @@ int ppg_stream_push_batch(PpgStream* st, const void* chunk, int nmax, const int*
         a.rowmap = reinterpret_cast<const int*>(st->d_tables + map_off[1]); a.map_blocks = nmap[1];
         LAUNCH_OK(ppg::launch_linear(prec, EPI_OUTCONV, 3, 1, a, 1, s), "stream out-conv+softmax");
     }
-    }   // (eager or capturing)
-    if (const int rc = finish(PPG_OK)) return rc;
-#undef LAUNCH_OK
     HIP_OK(hipEventRecord(st->uploaded[slot_index], s));
-    if (st->graph_steps) {
-        HIP_OK(hipEventRecord(st->ev_join, s));
-        HIP_OK(hipStreamWaitEvent(caller, st->ev_join, 0));
-    }
     st->received.swap(received); st->x_valid.swap(x_valid); st->o_valid.swap(o_valid); st->finished.swap(finished);
     return PPG_OK;
 }
@@ -2430,15 +2373,12 @@ int ppg_w2v2_body_forward(PpgW2v2Body* m, const float* features, const int64_t* 
     const int h = body_first_half(m, batch, frames);
     if (!h) return body_forward_one(m, m->slot[0], features, valid_frames, batch, frames, out, workspace, workspace_bytes, s);
     const size_t ws0 = align_up(body_layout(m, h, frames).total, 256);
-    HIP_OK(hipEventRecord(m->ev_fork, s));
-    HIP_OK(hipStreamWaitEvent(m->side, m->ev_fork, 0));
-    int rc = body_forward_one(m, m->slot[1], features + (size_t)h * frames * 512, valid_frames + h, batch - h, frames,
-                              out + (size_t)h * frames * m->hidden, static_cast<char*>(workspace) + ws0, workspace_bytes - ws0, m->side);
-    if (rc) return rc;
-    HIP_OK(hipEventRecord(m->ev_join, m->side));
-    rc = body_forward_one(m, m->slot[0], features, valid_frames, h, frames, out, workspace, ws0, s);
-    HIP_OK(hipStreamWaitEvent(s, m->ev_join, 0));
-    return rc;
+    return fork_join(s, m->ev_fork, &m->side, &m->ev_join, 1, [&]() -> int {
+        const int rc = body_forward_one(m, m->slot[1], features + (size_t)h * frames * 512, valid_frames + h, batch - h, frames,
+                                        out + (size_t)h * frames * m->hidden, static_cast<char*>(workspace) + ws0, workspace_bytes - ws0, m->side);
+        if (rc) return rc;
+        return body_forward_one(m, m->slot[0], features, valid_frames, h, frames, out, workspace, ws0, s);
+    });
 }
 
 namespace {
@@ -2493,11 +2433,6 @@ int body_forward_one(PpgW2v2Body* m, PpgW2v2Body::Slot& slot, const float* featu
     const char* act_x = op_copy ? Xb : reinterpret_cast<const char*>(X);
     char* xb_out = op_copy ? Xb : nullptr;
 
-#define LAUNCH_OK(expr, what)                                                        \
-    do {                                                                             \
-        hipError_t he_ = (expr);                                                     \
-        if (he_ != hipSuccess) return fail(PPG_EDEVICE, "%s: %s", what, hipGetErrorString(he_)); \
-    } while (0)
     // tokens per wave (16 nt).  Measured at 16 x 499 frames, bf16: nt 1 4.41 ms, nt 2 4.82 ms, nt 3 6.35 ms
     int nt = std::min(choose_nt(E, M, 2), 2);
     nt = std::max(1, std::min(ppg::env_experiment("PPGS_AMD_W2V2_NT", nt), sz == 2 ? 3 : 2));
@@ -2598,7 +2533,6 @@ int body_forward_one(PpgW2v2Body* m, PpgW2v2Body::Slot& slot, const float* featu
             LAUNCH_OK(layer_norm(d.g2, d.e2), "w2v2 LayerNorm 2");
         }
     }
-#undef LAUNCH_OK
     HIP_OK(hipMemcpy2DAsync(out, (size_t)frames * H * 4, X, (size_t)R * H * 4, (size_t)frames * H * 4, batch, hipMemcpyDeviceToDevice, s));
     return PPG_OK;
 }
