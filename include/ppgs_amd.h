@@ -228,6 +228,48 @@ int ppg_frontend(int device, const float* audio, int batch, int samples,
                  void* spec, void* mel, void* stream);
 
 /*
+ * Incremental frontend: the same mel frames as ppg_frontend, BIT FOR BIT, for `batch` recordings whose samples
+ * arrive in pieces (a microphone, a socket, live calls) -- what ppg_stream_push / ppg_stream_push_batch need as
+ * input.  No reference counterpart (ppgs/preprocess/mel.py works on finished recordings).  16 kHz samples only.
+ *
+ * Frame t reads samples 160 t - 432 .. 160 t + 591 of the reflect-padded recording, so it is computable once
+ * 160 t + 592 samples have arrived; the transform works on frame pairs (2 j, 2 j + 1), whose roundings depend on each
+ * other, so frames leave in those pairs.  ppg_audio_stream_frames (host only, usable without a device) is that rule:
+ * the frames emitted after `received` samples = ((received - 592) / 160 + 1) & ~1 (0 below 592 samples) while the
+ * recording goes on, received / 160 once it has ended (`flushed`) -- the rest then takes the right reflection about
+ * the last sample, as ppg_frontend computes it.  A recording must end with more than 432 samples (PPG_EINVAL
+ * otherwise, as ppg_frontend).  An item keeps only the samples its next frames need (< 1344 + one push), on the
+ * device: a stream runs in constant memory for any length.
+ *
+ * ppg_frontend_stream_push:
+ *   audio       : device fp32 (batch, n_max) with `audio_pitch` floats between rows; may be NULL when n_max = 0
+ *   counts_host : HOST int[batch], samples of item b that are new: [0, n_max], n_max <= max_push_samples
+ *                 (0 and no flush: the item sits this push out)
+ *   flush_host  : HOST int[batch] or NULL: item b's recording ends with this push's samples
+ *   mel         : device fp16 (batch, 80, k_max) with `mel_pitch` halves between the 80 rows of an item (item b at
+ *                 mel + b * 80 * mel_pitch): item b's new frames in columns [0, num_frames[b]); the other columns
+ *                 are not written.  PPG_EINVAL when an item has more than k_max new frames (ppg_audio_stream_frames
+ *                 tells beforehand); may be NULL when no item has any
+ *   first_frame : HOST int64[batch] or NULL: index, in item b's recording, of its first new frame
+ *   num_frames  : HOST int[batch] or NULL
+ * One kernel launch per 64 items on `hip_stream`, no host synchronisation; pushes of one object must be ordered
+ * (one stream, or events between them).  Pushing to an item after its flush is PPG_EINVAL until
+ * ppg_frontend_stream_reset(stream, item) (item -1: all) makes it ready for the next recording.  A failed push
+ * leaves every item as it was.  ppg_frontend_stream_state: per item (HOST int64[batch], either may be NULL) the
+ * samples received and the frames emitted so far.
+ */
+typedef struct PpgFrontendStream PpgFrontendStream;
+int64_t ppg_audio_stream_frames(int64_t received, int flushed);
+int ppg_frontend_stream_create(int device, int batch, int max_push_samples, PpgFrontendStream** stream);
+void ppg_frontend_stream_destroy(PpgFrontendStream* stream);
+int ppg_frontend_stream_batch(const PpgFrontendStream* stream);
+int ppg_frontend_stream_state(const PpgFrontendStream* stream, int64_t* received, int64_t* emitted);
+int ppg_frontend_stream_reset(PpgFrontendStream* stream, int item);
+int ppg_frontend_stream_push(PpgFrontendStream* stream, const float* audio, int64_t audio_pitch, int n_max,
+                             const int* counts_host, const int* flush_host, void* mel, int64_t mel_pitch, int k_max,
+                             int64_t* first_frame, int* num_frames, void* hip_stream);
+
+/*
  * Sample-rate conversion on the device: replaces ppgs.resample
  * (ppgs/core.py:599-608 = torchaudio.transforms.Resample with its defaults:
  * Hann-windowed sinc, lowpass_filter_width 6, rolloff 0.99), which the

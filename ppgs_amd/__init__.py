@@ -13,5 +13,6 @@ from .core import (                   # noqa: F401
     distance, interpolate, sparsify,
     representation_file_extension, engine_for, clear_cache)
 from . import core, distributed, edit      # noqa: F401
+from .engine import FrontendStream, audio_stream_frames   # noqa: F401
 
 __version__ = '0.1.0'

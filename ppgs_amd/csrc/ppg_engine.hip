@@ -2583,6 +2583,153 @@ int ppg_frontend(int device, const float* audio, int batch, int samples, void* s
     return PPG_OK;
 }
 
+// ----------------------------------------------------------------------------
+// Incremental frontend: audio arrives in pieces, mel frames leave as they become computable
+// ----------------------------------------------------------------------------
+int64_t ppg_audio_stream_frames(int64_t received, int flushed) {
+    if (received < 0) return -1;
+    if (flushed) return received / 160;
+    // frame t reads samples up to 160 t + 591; frames leave in the pairs (2 j, 2 j + 1) the transform forms
+    const int64_t computable = received < 592 ? 0 : (received - 592) / 160 + 1;
+    return computable & ~(int64_t)1;
+}
+
+struct PpgFrontendStream {
+    int device = 0, batch = 0, max_push = 0, cap = 0;
+    float* carry = nullptr;              // (batch, 2, cap): per item the current carry and the one the next push writes
+    struct Item {
+        int64_t received = 0, frontier = 0, base = 0;   // samples so far; frames emitted; sample index of carry[0]
+        int cur = 0;
+        bool flushed = false;
+    };
+    std::vector<Item> items;
+    std::mutex mu;
+};
+
+namespace {
+// first sample a recording with frame frontier f still needs: frame f starts at 160 f - 432
+int64_t carry_base(int64_t frontier) { return std::max<int64_t>(160 * frontier - 432, 0); }
+}  // namespace
+
+int ppg_frontend_stream_create(int device, int batch, int max_push_samples, PpgFrontendStream** out) {
+    if (!out || batch <= 0 || max_push_samples <= 0) return fail(PPG_EINVAL, "frontend stream: batch %d, max_push_samples %d", batch, max_push_samples);
+    if (max_push_samples > (1 << 28)) return fail(PPG_EINVAL, "frontend stream: max_push_samples %d is too large", max_push_samples);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(PPG_EDEVICE, "no HIP device: the PPG frontend has no CPU path");
+    Frontend* f = nullptr;
+    const int rc = frontend_for(device, &f);
+    if (rc) return rc;
+    HIP_OK(hipSetDevice(device));
+    std::unique_ptr<PpgFrontendStream> st(new PpgFrontendStream);
+    st->device = device; st->batch = batch; st->max_push = max_push_samples;
+    // before a push an item holds the samples from carry_base(frontier) on: fewer than 432 + 592 + 2 x 160 = 1344
+    // (the next pair is not computable yet); a push appends its own
+    st->cap = round_up(1344 + max_push_samples, 64);
+    st->items.resize(batch);
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&st->carry), (size_t)batch * 2 * st->cap * sizeof(float)));
+    *out = st.release();
+    return PPG_OK;
+}
+
+void ppg_frontend_stream_destroy(PpgFrontendStream* st) {
+    if (!st) return;
+    if (st->carry) { (void)hipSetDevice(st->device); (void)hipFree(st->carry); }
+    delete st;
+}
+
+int ppg_frontend_stream_batch(const PpgFrontendStream* st) { return st ? st->batch : fail(PPG_EINVAL, "null frontend stream"); }
+
+int ppg_frontend_stream_state(const PpgFrontendStream* st, int64_t* received, int64_t* emitted) {
+    if (!st) return fail(PPG_EINVAL, "null frontend stream");
+    for (int b = 0; b < st->batch; ++b) {
+        if (received) received[b] = st->items[b].received;
+        if (emitted) emitted[b] = st->items[b].frontier;
+    }
+    return PPG_OK;
+}
+
+int ppg_frontend_stream_reset(PpgFrontendStream* st, int item) {
+    if (!st || item < -1 || item >= st->batch) return fail(PPG_EINVAL, "frontend stream reset: item %d", item);
+    std::lock_guard<std::mutex> lock(st->mu);
+    for (int b = 0; b < st->batch; ++b) {
+        if (item >= 0 && b != item) continue;
+        const int cur = st->items[b].cur;             // (an earlier push may still be writing the other buffer: keep the roles)
+        st->items[b] = PpgFrontendStream::Item{};
+        st->items[b].cur = cur;
+    }
+    return PPG_OK;
+}
+
+int ppg_frontend_stream_push(PpgFrontendStream* st, const float* audio, int64_t audio_pitch, int n_max, const int* counts_host,
+                             const int* flush_host, void* mel, int64_t mel_pitch, int k_max, int64_t* first_frame, int* num_frames,
+                             void* stream) {
+    if (!st || !counts_host || n_max < 0 || k_max < 0) return fail(PPG_EINVAL, "frontend stream push: bad argument");
+    if (n_max > st->max_push) return fail(PPG_EINVAL, "frontend stream push: %d samples, the stream was created for pushes of <= %d", n_max, st->max_push);
+    if (n_max > 0 && (!audio || audio_pitch < n_max)) return fail(PPG_EINVAL, "frontend stream push: audio %p with pitch %lld for %d samples", (const void*)audio, (long long)audio_pitch, n_max);
+    std::lock_guard<std::mutex> lock(st->mu);
+    // everything is checked before any item's state changes
+    int most = 0;
+    for (int b = 0; b < st->batch; ++b) {
+        const PpgFrontendStream::Item& it = st->items[b];
+        const int n = counts_host[b], fl = flush_host ? flush_host[b] : 0;
+        if (n < 0 || n > n_max) return fail(PPG_EINVAL, "frontend stream push: counts[%d] = %d outside [0, %d]", b, n, n_max);
+        if (n == 0 && !fl) continue;
+        if (it.flushed) return fail(PPG_EINVAL, "frontend stream push: item %d was flushed (reset it for the next utterance)", b);
+        if (fl && it.received + n <= 432)
+            return fail(PPG_EINVAL, "frontend stream push: item %d ends after %lld samples: reflect padding of 432 needs more than 432 samples", b, (long long)(it.received + n));
+        most = std::max<int64_t>(most, ppg_audio_stream_frames(it.received + n, fl) - it.frontier);
+    }
+    if (most > k_max) return fail(PPG_EINVAL, "frontend stream push: %d new frames, the output holds %d", most, k_max);
+    if (most > 0 && (!mel || mel_pitch < most)) return fail(PPG_EINVAL, "frontend stream push: output %p with pitch %lld for %d frames", mel, (long long)mel_pitch, most);
+    if ((double)st->batch * 80.0 * (double)std::max<int64_t>(mel_pitch, 1) >= 4294967296.0)
+        return fail(PPG_EINVAL, "frontend stream push: batch %d x 80 x pitch %lld does not fit the kernel's 32-bit output index", st->batch, (long long)mel_pitch);
+    Frontend* f = nullptr;
+    int rc = frontend_for(st->device, &f);
+    if (rc) return rc;
+    HIP_OK(hipSetDevice(st->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int b0 = 0; b0 < st->batch; b0 += ppg::kFrontendStreamItems) {
+        const int items = std::min(ppg::kFrontendStreamItems, st->batch - b0);
+        ppg::FrontendStreamArgs a{};
+        a.chunk = audio; a.chunk_pitch = (long)audio_pitch; a.carry = st->carry; a.cap = st->cap; a.item0 = b0;
+        a.out_pitch = (int)mel_pitch;
+        int frames_most = 0;
+        bool any = false;
+        for (int l = 0; l < items; ++l) {
+            PpgFrontendStream::Item& it = st->items[b0 + l];
+            const int n = counts_host[b0 + l], fl = flush_host ? flush_host[b0 + l] : 0;
+            ppg::FrontendStreamItem& d = a.item[l];
+            if (first_frame) first_frame[b0 + l] = it.frontier;
+            if (num_frames) num_frames[b0 + l] = 0;
+            if (n == 0 && !fl) continue;                       // (all zero: no frames, nothing carried, no sample read)
+            const int64_t origin = 160 * it.frontier, total = it.received + n;
+            const int64_t frontier = ppg_audio_stream_frames(total, fl);
+            d.lo = (int)std::max<int64_t>(-origin, -(1 << 29));
+            d.hi = (int)(total - origin);
+            d.cbase = (int)(it.base - origin);
+            d.split = (int)(it.received - origin);
+            d.frames = (int)(frontier - it.frontier);
+            d.keep = fl ? d.hi : (int)(carry_base(frontier) - origin);
+            d.cur = it.cur;
+            if (d.hi - d.keep > st->cap || d.split - d.cbase > st->cap || d.keep < d.cbase)
+                return fail(PPG_EINVAL, "frontend stream push: item %d carry [%d, %d) of [%d, %d) does not fit %d samples (internal)", b0 + l, d.keep, d.hi, d.cbase, d.hi, st->cap);
+            if (num_frames) num_frames[b0 + l] = d.frames;
+            frames_most = std::max(frames_most, d.frames);
+            any = true;
+            it.received = total;
+            it.frontier = frontier;
+            it.flushed = fl != 0;
+            if (!fl) { it.base = carry_base(frontier); it.cur ^= 1; }
+        }
+        if (!any) continue;
+        a.groups_per_item = std::max(1, (frames_most + ppg::kFrontendFrames - 1) / ppg::kFrontendFrames);
+        const hipError_t he = ppg::launch_frontend_stream(f->tb, a, items, mel, s);
+        if (he != hipSuccess) return fail(PPG_EDEVICE, "frontend stream: %s", hipGetErrorString(he));
+    }
+    return PPG_OK;
+}
+
 int ppg_engine_nonfinite(PpgEngine* e, int clear, int* flag) {
     if (!e || !flag) return fail(PPG_EINVAL, "null argument");
     if (!e->d_overflow) { *flag = 0; return PPG_OK; }

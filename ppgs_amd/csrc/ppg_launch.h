@@ -94,4 +94,30 @@ struct FrontendTables {
 hipError_t launch_frontend(const FrontendTables& tb, const float* audio, int batch, int samples,
                            void* spec, void* mel, hipStream_t s);
 
+// Incremental frontend (ppg_frontend_stream_*): one launch computes, for up to kFrontendStreamItems items, the mel
+// frames that this push's samples completed.  Per item, positions relative to sample 160 f of its recording (f: the
+// item's even frame frontier before the push, so new frame k starts at 160 k - 432):
+struct FrontendStreamItem {
+    int lo;        // sample 0 of the recording (-160 f, clamped): positions below it reflect about it
+    int hi;        // one past the last sample received, this push included: positions from it on reflect about hi - 1
+    int cbase;     // first position the item's current carry buffer holds; [cbase, split) is the carry
+    int split;     // [split, hi) are this push's samples
+    int frames;    // new frames to compute: 0 .. frames - 1
+    int keep;      // [keep, hi) is carried to the next push (keep = hi: nothing)
+    int cur;       // which of the item's two carry buffers is current; the other one receives [keep, hi)
+    int pad;
+};
+constexpr int kFrontendStreamItems = 64;
+struct FrontendStreamArgs {
+    const float* chunk;       // (items, chunk_pitch) fp32: this push's samples
+    float* carry;             // (items, 2, cap) fp32
+    long chunk_pitch;
+    int cap;
+    int item0;                // batch index of item[0] (rows of chunk, carry and the output)
+    int groups_per_item;      // 16-frame groups per item = ceil(max frames / 16), >= 1
+    int out_pitch;            // output: fp16 (items, 80, out_pitch), new frame k in column k
+    FrontendStreamItem item[kFrontendStreamItems];
+};
+hipError_t launch_frontend_stream(const FrontendTables& tb, const FrontendStreamArgs& args, int items, void* mel, hipStream_t s);
+
 }  // namespace ppg

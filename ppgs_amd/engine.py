@@ -109,6 +109,17 @@ SYMBOLS = {
     'ppg_frontend': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_audio_stream_frames': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int]),
+    'ppg_frontend_stream_create': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    'ppg_frontend_stream_destroy': (None, [ctypes.c_void_p]),
+    'ppg_frontend_stream_batch': (ctypes.c_int, [ctypes.c_void_p]),
+    'ppg_frontend_stream_state': (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P]),
+    'ppg_frontend_stream_reset': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'ppg_frontend_stream_push': (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+        ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, _I64P,
+        ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]),
     'ppg_resample_length': (ctypes.c_int64, [
         ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'ppg_resample': (ctypes.c_int, [
@@ -277,6 +288,7 @@ class Engine:
         self.hidden_channels = hidden
         self.output_channels = state['output_layer.weight'].shape[0]
         self.precision = precision
+        self.is_causal = bool(is_causal)
         self.device = torch.device('cuda', device)
         cfg = PpgConfig(
             input_channels=cin, hidden_channels=hidden, num_layers=layers,
@@ -370,6 +382,18 @@ class Engine:
         """A KV-cached causal stream over an utterance of any length > 500 frames
         (see LongStream); the engine must be causal."""
         return LongStream(self, dtype)
+
+    def audio_stream(self, max_frames, max_push_samples=16000):
+        """Stream.push for raw 16 kHz samples (see AudioStream): causal engines with 80 input channels."""
+        return AudioStream(self, max_frames, max_push_samples)
+
+    def batched_audio_stream(self, batch, max_frames, max_push_samples=16000):
+        """BatchedStream.push for raw 16 kHz samples (see BatchedAudioStream)."""
+        return BatchedAudioStream(self, batch, max_frames, max_push_samples)
+
+    def long_audio_stream(self, max_push_samples=16000):
+        """LongStream.push for raw 16 kHz samples (see LongAudioStream)."""
+        return LongAudioStream(self, max_push_samples)
 
     def encode(self, features, lengths, softmax=True, legacy_mode=False,
                workspace=None):
@@ -600,6 +624,168 @@ def grid_sample(ppg, grid):
 
 class PpgW2v2Weights(ctypes.Structure):
     _fields_ = [('conv_weight', _FP * 7), ('norm_weight', _FP), ('norm_bias', _FP)]
+
+
+def audio_stream_frames(received, flushed=False):
+    """Mel frames the incremental frontend has emitted after `received` samples of a recording
+    (ppg_audio_stream_frames, host only): frame t needs samples up to 160 t + 591 and frames leave in the
+    pairs (2 j, 2 j + 1) the transform works on, so ((received - 592) // 160 + 1) & ~1 while the recording
+    goes on (0 below 592 samples) and received // 160 once it has ended."""
+    return int(library().ppg_audio_stream_frames(int(received), int(bool(flushed))))
+
+
+class FrontendStream:
+    """The mel frontend for audio that arrives in pieces (include/ppgs_amd.h: ppg_frontend_stream_*): `batch`
+    recordings, each handed its new 16 kHz samples push by push, each returning the mel frames that became
+    computable -- the frames :func:`frontend` computes for the whole recording, bit for bit.  A frame needs 592
+    samples past its start and leaves together with its pair partner (audio_stream_frames); flush ends a
+    recording (its last frames take the reflection about the last sample; it must have more than 432 samples).
+    Only the samples the next frames need stay on the device.  Pushes of one object must be ordered on the device
+    (one HIP stream, or events between them).  16 kHz only: there is no streaming resampler."""
+
+    def __init__(self, batch, max_push_samples, device=0):
+        if not torch.cuda.is_available():
+            raise PpgError('ppgs_amd: no HIP device visible; the frontend has no CPU path')
+        self.device = device if isinstance(device, torch.device) else torch.device('cuda', device)
+        self.batch, self.max_push_samples = int(batch), int(max_push_samples)
+        self._lib = library()
+        handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(self._lib.ppg_frontend_stream_create(
+                self.device.index, self.batch, self.max_push_samples, ctypes.byref(handle)))
+        self._handle = handle
+
+    def __del__(self):
+        handle, self._handle = getattr(self, '_handle', None), None
+        if handle:
+            self._lib.ppg_frontend_stream_destroy(handle)
+
+    def _state(self):
+        received, emitted = (ctypes.c_int64 * self.batch)(), (ctypes.c_int64 * self.batch)()
+        _check(self._lib.ppg_frontend_stream_state(self._handle, received, emitted))
+        return list(received), list(emitted)
+
+    @property
+    def received(self):
+        """samples received so far, per item"""
+        return self._state()[0]
+
+    @property
+    def emitted(self):
+        """mel frames emitted so far, per item"""
+        return self._state()[1]
+
+    def reset(self, item=None):
+        """Make item `item` (default: every item) ready for its next recording."""
+        _check(self._lib.ppg_frontend_stream_reset(self._handle, -1 if item is None else int(item)))
+
+    def push(self, audio, counts=None, flush=False):
+        """audio (batch, n_max) or (batch, 1, n_max) fp32 on the device (None: no samples, only flushes),
+        counts[b] <= n_max new samples of item b (default n_max; 0 without flush: the item sits out), flush: bool
+        or one per item -> (mel fp16 (batch, 80, k_max), frames): item b's new frames are mel[b, :, :frames[b]]
+        (the columns behind them are zero), k_max = max(frames)."""
+        if audio is None:
+            audio = torch.empty(self.batch, 0, dtype=torch.float32, device=self.device)
+        if audio.dim() == 3 and audio.shape[1] == 1:
+            audio = audio[:, 0]
+        if audio.dim() != 2 or audio.shape[0] != self.batch:
+            raise ValueError(f'audio must be ({self.batch}, samples), got {tuple(audio.shape)}')
+        audio = audio.to(device=self.device, dtype=torch.float32)
+        if audio.shape[1] and (audio.stride(1) != 1 or (self.batch > 1 and audio.stride(0) < audio.shape[1])):
+            audio = audio.contiguous()
+        nmax = audio.shape[1]
+        counts = [nmax] * self.batch if counts is None else [int(n) for n in counts]
+        flushes = [bool(flush)] * self.batch if isinstance(flush, bool) else [bool(f) for f in flush]
+        if len(counts) != self.batch or len(flushes) != self.batch:
+            raise ValueError('counts / flush need one entry per item')
+        received, emitted = self._state()
+        new = [audio_stream_frames(received[b] + counts[b], flushes[b]) - emitted[b] if counts[b] or flushes[b] else 0
+               for b in range(self.batch)]
+        kmax = max(max(new), 0)
+        array = ctypes.c_int * self.batch
+        frames = array()
+        with torch.cuda.device(self.device):
+            ragged = any(k != kmax for k in new)
+            mel = (torch.zeros if ragged else torch.empty)(
+                (self.batch, config.NUM_MELS, kmax), dtype=torch.float16, device=self.device)
+            _check(self._lib.ppg_frontend_stream_push(
+                self._handle, ctypes.c_void_p(audio.data_ptr()) if nmax else None,
+                audio.stride(0) if nmax else 0, nmax, array(*counts), array(*[int(f) for f in flushes]),
+                ctypes.c_void_p(mel.data_ptr()) if kmax else None, kmax, kmax, None, frames,
+                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return mel, list(frames)
+
+
+def _audio_engine(engine):
+    if not engine.is_causal:
+        raise ValueError('audio streams need a causal engine (is_causal=True), like Engine.stream')
+    if engine.input_channels != config.NUM_MELS:
+        raise ValueError(f'audio streams feed mel frames: the engine has {engine.input_channels} input channels, not {config.NUM_MELS}')
+
+
+class AudioStream:
+    """:class:`Stream` fed with raw 16 kHz samples: a :class:`FrontendStream` turns each piece into the mel
+    frames it completed and the KV-cached stream emits the posteriors that became final.  Equal to Stream pushed
+    with the mel of the whole recording in the same frame pieces.  Latency: 592 samples of look-ahead, up to one
+    hop while a frame waits for its pair partner, and the model's 4 frames.  16 kHz only (no streaming
+    resampler); causal engines with 80 input channels."""
+
+    def __init__(self, engine, max_frames, max_push_samples=16000):
+        _audio_engine(engine)
+        self.engine = engine
+        self.frontend = FrontendStream(1, max_push_samples, engine.device)
+        self.stream = self._make_stream(engine, max_frames)
+
+    @staticmethod
+    def _make_stream(engine, max_frames):
+        return Stream(engine, max_frames, torch.float16)
+
+    def push(self, samples, flush=False, softmax=True):
+        """samples (n,), (1, n) or (1, 1, n) fp32 (None or n = 0 with flush=True to just end the recording) ->
+        (40, k) fp32: the posteriors of the k frames that became final."""
+        engine = self.engine
+        if samples is None:
+            samples = torch.empty(0, dtype=torch.float32, device=engine.device)
+        samples = samples.reshape(1, -1)
+        step = self.frontend.max_push_samples
+        pieces = []
+        for start in range(0, max(samples.shape[1], 1), step):
+            last = start + step >= samples.shape[1]
+            mel, frames = self.frontend.push(samples[:, start:start + step], flush=flush and last)
+            if frames[0] or (flush and last):
+                pieces.append(self.stream.push(mel[0, :, :frames[0]], flush=flush and last, softmax=softmax))
+        if not pieces:
+            return torch.empty(engine.output_channels, 0, dtype=torch.float32, device=engine.device)
+        return pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=1)
+
+
+class LongAudioStream(AudioStream):
+    """:class:`LongStream` (an utterance of more than 500 frames, as the reference chunks it) fed with raw
+    16 kHz samples; see :class:`AudioStream`."""
+
+    def __init__(self, engine, max_push_samples=16000):
+        super().__init__(engine, None, max_push_samples)
+
+    @staticmethod
+    def _make_stream(engine, max_frames):
+        return LongStream(engine, torch.float16)
+
+
+class BatchedAudioStream:
+    """:class:`BatchedStream` fed with raw 16 kHz samples: one incremental-frontend launch and one model step
+    advance all `batch` recordings, each by its own number of samples; see :class:`AudioStream`."""
+
+    def __init__(self, engine, batch, max_frames, max_push_samples=16000):
+        _audio_engine(engine)
+        self.engine, self.batch = engine, int(batch)
+        self.frontend = FrontendStream(batch, max_push_samples, engine.device)
+        self.stream = BatchedStream(engine, batch, max_frames, torch.float16)
+
+    def push(self, samples, counts=None, flush=False, softmax=True):
+        """samples (batch, n_max) fp32, n_max <= max_push_samples (None: only flushes), counts[b] new samples of
+        item b, flush: bool or one per item -> a list of (40, k_b) fp32 tensors, as BatchedStream.push."""
+        mel, frames = self.frontend.push(samples, counts, flush)
+        return self.stream.push(mel, frames, flush, softmax)
 
 
 class Stream:
