@@ -423,6 +423,67 @@ int ppg_grid_sample(int device, const float* ppg, int rows, int frames,
                     const float* grid, int length, float* out, void* stream);
 
 /*
+ * Frame metrics accumulated on the device: what the reference's `python -m ppgs.evaluate` computes per batch with
+ * five metric objects (ppgs/evaluate/metrics.py: Accuracy, CategoricalAccuracy, JensenShannon, TopKAccuracy, Loss,
+ * DistanceMatrix), here ONE kernel launch per batch into one device block, no host synchronisation, read once at
+ * the end.
+ *
+ * PpgMetricsState is that block (device memory owned by the caller, 8-byte aligned, ppg_metrics_state_bytes() bytes).
+ * Every accumulator is a 64-bit integer, so a state is a function of the MULTISET of (frame, label) pairs it has
+ * seen and of nothing else: the same bits for any grid, stream, co-running work, split of the frames over update
+ * calls or order of the batches, and states of several devices merge by integer addition.  Counts are plain
+ * integers.  The real-valued sums (loss_sum, loss_weight_sum, jsd_sum, every matrix cell) are FIXED POINT in units
+ * of 2^-32: each frame's fp32 value v is rounded once, to nearest, to an integer multiple of 2^-32 (error <= 2^-33
+ * per frame and cell; v is first brought into [0, 2^20], NaN counting as 0) and added exactly; divide by 2^32 when
+ * reading.  A sum holds up to 2^31 (2.1e9), i.e. more than 5e8 frames at a mean loss of 4.
+ *
+ *   count, true_positives      frames that count; of those argmax(logits) == label               (Accuracy)
+ *   topk_correct               label among the k largest logits                                   (TopKAccuracy)
+ *   invalid_labels             frames whose label is neither -100 nor in [0, 40): ignored otherwise
+ *   class_total / class_count  per label: correct frames / frames              (CategoricalAccuracy, DistanceMatrix.count)
+ *   loss_sum                   sum of cross_entropy(logits, label) [* loss_weights[label]]        (Loss, ppgs.train.loss)
+ *   loss_weight_sum            sum of loss_weights[label] (0 without loss_weights)
+ *   jsd_sum                    sum of ppg_distance(softmax(logits), one_hot(label)), `mix` as there (JensenShannon)
+ *   distance_matrix[r][c]      r = argmax_p(softmax[p] * class_weights[p]): += softmax[c] * class_weights[c]
+ *   confusion[r][c]            r = label: += softmax[c].  NOT the reference's arithmetic on purpose: its
+ *                              ConfusionMatrix does `matrix[target] += probs`, an indexed assignment that keeps one
+ *                              of the frames that share a label instead of their sum; this one accumulates.
+ * Argmax and top-k ties resolve to the lowest index.
+ *
+ * ppg_metrics_update:
+ *   logits        : device fp32 (batch, 40, frames), e.g. ppg_encode with softmax = 0
+ *   labels        : device (batch, frames), int64 if label_is_int64 else int32; -100 = no label
+ *   lengths       : device int64[batch] or NULL; a frame counts when its label != -100 and t < lengths[b]
+ *                   (frames that do not count are never read: their logits may be anything)
+ *   k             : 1..8
+ *   mix           : device fp32 (40, 40) as ppg_distance's, or NULL
+ *   class_weights : device fp32 (40) or NULL (= 1);  loss_weights: device fp32 (40) or NULL (= 1)
+ * One launch on `stream`; no allocation, synchronisation or copy, so it can be captured into a graph.  Updates of one
+ * state may run concurrently on several streams.  ppg_metrics_reset zeroes the block on `stream`.
+ */
+#define PPG_METRICS_CLASSES 40
+typedef struct PpgMetricsState {
+    int64_t count;
+    int64_t true_positives;
+    int64_t topk_correct;
+    int64_t invalid_labels;
+    int64_t loss_sum;          /* 2^-32 */
+    int64_t loss_weight_sum;   /* 2^-32 */
+    int64_t jsd_sum;           /* 2^-32 */
+    int64_t reserved;
+    int64_t class_total[PPG_METRICS_CLASSES];
+    int64_t class_count[PPG_METRICS_CLASSES];
+    int64_t distance_matrix[PPG_METRICS_CLASSES][PPG_METRICS_CLASSES];   /* 2^-32 */
+    int64_t confusion[PPG_METRICS_CLASSES][PPG_METRICS_CLASSES];         /* 2^-32 */
+} PpgMetricsState;
+size_t ppg_metrics_state_bytes(void);
+int ppg_metrics_reset(int device, PpgMetricsState* state, void* stream);
+int ppg_metrics_update(int device, const float* logits, const void* labels, int label_is_int64,
+                       const int64_t* lengths, int batch, int frames, int k, const float* mix,
+                       const float* class_weights, const float* loss_weights, PpgMetricsState* state,
+                       void* stream);
+
+/*
  * Per-kernel-class timing with HIP events on the launch stream (used by
  * bench.py's roofline leg).  `classes` is a bitmask of (1 << PPG_K_*), 0 =
  * off, -1 = every class (each timed launch costs two event records on the

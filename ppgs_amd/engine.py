@@ -84,6 +84,15 @@ class PpgPlanInfo(ctypes.Structure):
         ('workspace_bytes', ctypes.c_size_t)]
 
 
+class PpgMetricsState(ctypes.Structure):
+    """The device block of ppg_metrics_update: 64-bit integers, real-valued sums in units of 2^-32."""
+    _fields_ = [(name, ctypes.c_int64) for name in (
+        'count', 'true_positives', 'topk_correct', 'invalid_labels', 'loss_sum', 'loss_weight_sum',
+        'jsd_sum', 'reserved')] + [
+        ('class_total', ctypes.c_int64 * 40), ('class_count', ctypes.c_int64 * 40),
+        ('distance_matrix', ctypes.c_int64 * 40 * 40), ('confusion', ctypes.c_int64 * 40 * 40)]
+
+
 # every symbol include/ppgs_amd.h declares: name -> (restype, argtypes)
 _I64P = ctypes.POINTER(ctypes.c_int64)
 SYMBOLS = {
@@ -134,6 +143,11 @@ SYMBOLS = {
     'ppg_grid_sample': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
         ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_metrics_state_bytes': (ctypes.c_size_t, []),
+    'ppg_metrics_reset': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_metrics_update': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_w2v2_body_create': (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     'ppg_w2v2_body_destroy': (None, [ctypes.c_void_p]),
@@ -620,6 +634,115 @@ def grid_sample(ppg, grid):
                 x.device.index, x.data_ptr(), rows, x.shape[-1], g.data_ptr(),
                 g.shape[0], out.data_ptr(), torch.cuda.current_stream().cuda_stream))
     return out      # fp32 also for half-precision PPGs: the reference's float grid promotes them
+
+
+METRICS_FIXED_POINT = 2.0 ** 32        # the real-valued accumulators of PpgMetricsState count units of 2^-32
+
+
+def metrics_fields(words):
+    """PpgMetricsState as a dict, from its int64 words (numpy, length sizeof / 8): Python ints for the scalars,
+    int64 arrays for the per-class counts and the two matrices.  Fixed-point fields stay integers (exact); divide
+    by METRICS_FIXED_POINT for their value."""
+    out, offset = {}, 0
+    for name, kind in PpgMetricsState._fields_:
+        size = ctypes.sizeof(kind) // 8
+        if size == 1:
+            out[name] = int(words[offset])
+        elif size == 40:
+            out[name] = words[offset:offset + size].copy()
+        else:
+            out[name] = words[offset:offset + size].reshape(40, 40).copy()
+        offset += size
+    del out['reserved']
+    return out
+
+
+class MetricsState:
+    """Frame metrics accumulated on the GPU (ppg_metrics_update): update() is one kernel launch on the current
+    stream and synchronises nothing; read() is the only place that does.  The state is a function of the multiset
+    of (frame, label) pairs seen, bit for bit, however they were split over updates, streams or devices."""
+
+    def __init__(self, device=0, k=3, similarity_mix=None, class_weights=None, loss_weights=None):
+        if not torch.cuda.is_available():
+            raise PpgError('ppgs_amd: no HIP device visible; the metrics have no CPU path')
+        if not 1 <= int(k) <= 8:
+            raise ValueError(f'top-k needs 1 <= k <= 8, got {k}')
+        self._lib = library()
+        self.device = torch.device('cuda', device) if isinstance(device, int) else torch.device(device)
+        self.k = int(k)
+
+        def table(tensor, shape):
+            if tensor is None:
+                return None
+            tensor = torch.as_tensor(tensor).to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(tensor.shape) != shape:
+                raise ValueError(f'expected a tensor of shape {shape}, got {tuple(tensor.shape)}')
+            return tensor
+        self.similarity_mix = table(similarity_mix, (40, 40))
+        self.class_weights = table(class_weights, (40,))
+        self.loss_weights = table(loss_weights, (40,))
+        assert ctypes.sizeof(PpgMetricsState) == self._lib.ppg_metrics_state_bytes()
+        self.state = torch.zeros(ctypes.sizeof(PpgMetricsState) // 8, dtype=torch.int64, device=self.device)
+
+    def reset(self):
+        with torch.cuda.device(self.device):
+            _check(self._lib.ppg_metrics_reset(
+                self.device.index, self.state.data_ptr(), torch.cuda.current_stream().cuda_stream))
+
+    def _on_device(self, tensor, dtype=None):
+        tensor = torch.as_tensor(tensor)
+        if not tensor.is_cuda:            # a host tensor goes through pinned memory: the copy is asynchronous too
+            tensor = tensor.contiguous().pin_memory()
+        return tensor.to(device=self.device, dtype=dtype, non_blocking=True).contiguous()
+
+    def update(self, logits, labels, lengths=None):
+        """logits (batch, 40, frames) fp32 on this device, labels (batch, frames) int64 / int32 (-100: no label),
+        lengths (batch,) or None.  Labels and lengths on the device are used where they lie."""
+        if not (torch.is_tensor(logits) and logits.is_cuda and logits.device == self.device):
+            raise PpgError('ppgs_amd: the metrics work on logits on their own HIP device')
+        if logits.dim() != 3 or logits.shape[1] != 40:
+            raise ValueError(f'logits must be (batch, 40, frames), got {tuple(logits.shape)}')
+        logits = logits.to(torch.float32).contiguous()
+        batch, _, frames = logits.shape
+        labels = self._on_device(labels)
+        if labels.dtype != torch.int32:
+            labels = labels.to(torch.int64)
+        if tuple(labels.shape) != (batch, frames):
+            raise ValueError(f'labels must be ({batch}, {frames}), got {tuple(labels.shape)}')
+        if lengths is not None:
+            lengths = self._on_device(lengths, torch.int64).reshape(-1)
+            if lengths.numel() != batch:
+                raise ValueError(f'lengths has {lengths.numel()} entries for a batch of {batch}')
+
+        def pointer(tensor):
+            return tensor.data_ptr() if tensor is not None else None
+        with torch.cuda.device(self.device):
+            _check(self._lib.ppg_metrics_update(
+                self.device.index, logits.data_ptr(), labels.data_ptr(), int(labels.dtype == torch.int64),
+                pointer(lengths), batch, frames, self.k, pointer(self.similarity_mix), pointer(self.class_weights),
+                pointer(self.loss_weights), self.state.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        if not torch.cuda.is_current_stream_capturing():
+            for tensor in (logits, labels, lengths):  # updates on a side stream: the allocator must not reuse them early
+                if tensor is not None:
+                    tensor.record_stream(torch.cuda.current_stream(self.device))
+
+    def read(self):
+        """The state as a dict (metrics_fields) plus 'k'; synchronises with the device."""
+        out = metrics_fields(self.state.cpu().numpy())
+        out['k'] = self.k
+        return out
+
+    @staticmethod
+    def merge(*reads):
+        """Sum of read() dicts (several ranks or devices): integer addition, so exact."""
+        out = dict(reads[0])
+        for other in reads[1:]:
+            if other['k'] != out['k']:
+                raise ValueError('states with different k do not merge')
+            for key, value in other.items():
+                if key != 'k':
+                    out[key] = out[key] + value
+        return out
 
 
 class PpgW2v2Weights(ctypes.Structure):

@@ -1,0 +1,4 @@
+"""Evaluation (reference ``python -m ppgs.evaluate``): frame metrics of a checkpoint against labels,
+accumulated on the GPU by one kernel launch per batch (``ppg_metrics_update``) and read once at the end."""
+from .metrics import Metrics, format_results, phoneme_weights   # noqa: F401
+from .core import across_precisions, from_dataloader, save      # noqa: F401
