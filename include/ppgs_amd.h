@@ -423,6 +423,44 @@ int ppg_grid_sample(int device, const float* ppg, int rows, int frames,
                     const float* grid, int length, float* out, void* stream);
 
 /*
+ * Dynamic time warping over the per-frame term of ppg_distance: the pronunciation distance, and the alignment, of
+ * two PPGs with different numbers of frames (no counterpart in the reference, which needs aligned PPGs).
+ *
+ *   C[i, j]  the ppg_distance term of frame i of X against frame j of Y (clamp, optional mix, sum of 40 roots).
+ *            Both sides' mixed frames come from one piece of code, so equal input frames cost exactly 0.
+ *   D[0, 0] = C[0, 0];  D[i, j] = C[i, j] + min(D[i-1, j-1], D[i-1, j], D[i, j-1]) in fp32, a predecessor outside
+ *            the table counting as +inf.  Ties go to the diagonal first, then (i-1, j), then (i, j-1); the minimum
+ *            is comparisons only.
+ *   total = D[Tx-1, Ty-1];  steps = K, the number of cells on that path, max(Tx, Ty) <= K <= Tx + Ty - 1.
+ *
+ * ppg_dtw:
+ *   ppg_x, ppg_y : device fp32 (pairs, 40, frames_x) and (pairs, 40, frames_y), padded to the longest item; pair b
+ *                  compares item b of each side; frames past an item's length are never read
+ *   lengths_x/_y : device int32[pairs], each in [1, frames_x] / [1, frames_y]
+ *   mix          : device fp32 (40, 40) as ppg_distance's, or NULL
+ *   total, steps : device fp32[pairs], int32[pairs]
+ *   path         : NULL (distance only: no direction table, no trace-back), or device int32
+ *                  (pairs, frames_x + frames_y - 1, 2): rows 0 .. K-1 of pair b are its (i, j) cells from (0, 0) to
+ *                  (Tx-1, Ty-1), the rest is left alone
+ *   path_length  : device int32[pairs] = K again, required with path
+ *   path_cost    : NULL, or device fp32 (pairs, frames_x + frames_y - 1): C along the path (needs path)
+ *   workspace    : device memory, 16-byte aligned, at least ppg_dtw_workspace_bytes(pairs, frames_x, frames_y,
+ *                  path != NULL) bytes: the prepared frames (320 B per frame), the cost table (4 B per cell, rows
+ *                  rounded up to 256 and columns + 63 to 64) and, with a path, one direction byte per cell
+ * Kernel launches on `stream` only: no allocation, synchronisation or copy.  Calls with workspaces of their own may
+ * run concurrently on several streams.
+ * Limits: PPG_DTW_MAX_FRAMES frames per side and PPG_DTW_MAX_PAIRS pairs per call (PPG_EINVAL above them;
+ * ppg_dtw_workspace_bytes, which is host-only, returns 0 for such arguments).
+ */
+#define PPG_DTW_MAX_FRAMES 4096
+#define PPG_DTW_MAX_PAIRS 65535
+size_t ppg_dtw_workspace_bytes(int pairs, int frames_x, int frames_y, int want_path);
+int ppg_dtw(int device, const float* ppg_x, int frames_x, const float* ppg_y, int frames_y, int pairs,
+            const int32_t* lengths_x, const int32_t* lengths_y, const float* mix, float* total, int32_t* steps,
+            int32_t* path, int32_t* path_length, float* path_cost, void* workspace, size_t workspace_bytes,
+            void* stream);
+
+/*
  * Frame metrics accumulated on the device: what the reference's `python -m ppgs.evaluate` computes per batch with
  * five metric objects (ppgs/evaluate/metrics.py: Accuracy, CategoricalAccuracy, JensenShannon, TopKAccuracy, Loss,
  * DistanceMatrix), here ONE kernel launch per batch into one device block, no host synchronisation, read once at

@@ -143,6 +143,11 @@ SYMBOLS = {
     'ppg_grid_sample': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
         ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_dtw_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_dtw': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'ppg_metrics_state_bytes': (ctypes.c_size_t, []),
     'ppg_metrics_reset': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_metrics_update': (ctypes.c_int, [
@@ -634,6 +639,56 @@ def grid_sample(ppg, grid):
                 x.device.index, x.data_ptr(), rows, x.shape[-1], g.data_ptr(),
                 g.shape[0], out.data_ptr(), torch.cuda.current_stream().cuda_stream))
     return out      # fp32 also for half-precision PPGs: the reference's float grid promotes them
+
+
+DTW_MAX_FRAMES = 4096          # PPG_DTW_MAX_FRAMES
+DTW_MAX_PAIRS = 65535          # PPG_DTW_MAX_PAIRS, per call of the library
+DTW_WORKSPACE_BYTES = 4 << 30  # a larger batch runs as several calls, each within this much workspace
+
+
+def dtw_pairs(ppg_x, ppg_y, lengths_x, lengths_y, mix=None, want_path=False, want_cost=False):
+    """Dynamic time warping of pair b = (ppg_x[b, :, :lengths_x[b]], ppg_y[b, :, :lengths_y[b]]) over the
+    per-frame term of ppg_distance (ppg_dtw): (pairs, 40, frames_x) and (pairs, 40, frames_y) on a GPU, lengths as
+    host integers -> total (pairs,) fp32, steps (pairs,) int32, and with want_path the padded paths
+    (pairs, frames_x + frames_y - 1, 2) int32 [and with want_cost the cell costs along them], else None."""
+    if not (ppg_x.is_cuda and ppg_y.is_cuda):
+        raise PpgError('ppgs_amd: the post-ops work on HIP device tensors')
+    x = ppg_x.to(torch.float32).contiguous()
+    y = ppg_y.to(torch.float32).contiguous()
+    if x.dim() != 3 or y.dim() != 3 or x.shape[1] != 40 or y.shape[1] != 40 or x.shape[0] != y.shape[0]:
+        raise ValueError(f'PPGs must be (pairs, 40, frames), got {tuple(x.shape)} and {tuple(y.shape)}')
+    pairs, frames_x, frames_y = x.shape[0], x.shape[2], y.shape[2]
+    if not (1 <= frames_x <= DTW_MAX_FRAMES and 1 <= frames_y <= DTW_MAX_FRAMES and pairs >= 1):
+        raise ValueError(f'dtw takes 1 to {DTW_MAX_FRAMES} frames per side, got {frames_x} and {frames_y}')
+    want_path = want_path or want_cost
+    device = x.device
+    if mix is not None:
+        mix = mix.to(device=device, dtype=torch.float32).contiguous()
+    lengths = torch.tensor([list(lengths_x), list(lengths_y)], dtype=torch.int32).to(device)
+    total = torch.empty((pairs,), dtype=torch.float32, device=device)
+    steps = torch.empty((pairs,), dtype=torch.int32, device=device)
+    longest = frames_x + frames_y - 1
+    path = torch.zeros((pairs, longest, 2), dtype=torch.int32, device=device) if want_path else None
+    path_length = torch.empty((pairs,), dtype=torch.int32, device=device) if want_path else None     # K again
+    cost = torch.zeros((pairs, longest), dtype=torch.float32, device=device) if want_cost else None
+    lib = library()
+    per_pair = lib.ppg_dtw_workspace_bytes(1, frames_x, frames_y, int(want_path))
+    group = max(1, min(pairs, DTW_MAX_PAIRS, DTW_WORKSPACE_BYTES // per_pair))
+    size = lib.ppg_dtw_workspace_bytes(group, frames_x, frames_y, int(want_path))
+    workspace = torch.empty((size,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for at in range(0, pairs, group):
+            count = min(group, pairs - at)
+            _check(lib.ppg_dtw(
+                device.index, x[at:].data_ptr(), frames_x, y[at:].data_ptr(), frames_y, count,
+                lengths[0, at:].data_ptr(), lengths[1, at:].data_ptr(),
+                mix.data_ptr() if mix is not None else None, total[at:].data_ptr(), steps[at:].data_ptr(),
+                path[at:].data_ptr() if want_path else None,
+                path_length[at:].data_ptr() if want_path else None,
+                cost[at:].data_ptr() if want_cost else None,
+                workspace.data_ptr(), size, stream))
+    return total, steps, path, cost
 
 
 METRICS_FIXED_POINT = 2.0 ** 32        # the real-valued accumulators of PpgMetricsState count units of 2^-32
