@@ -87,7 +87,10 @@ def seeded_state_dict(
 
     Matrices are U(-b, b) with b = sqrt(3 / fan_in) (unit-gain), biases
     U(-0.1, 0.1), LayerNorm affine = 1 + 0.1 N(0,1) / 0.1 N(0,1) so that no
-    parameter is at a value (0 or 1) that would hide an indexing bug.
+    parameter is at a value (0 or 1) that would hide an indexing bug.  The
+    same rule covers the wav2vec 2.0 engines: ``tests/w2v2_params.py``'s
+    ``perturb`` applies it to an HF ``Wav2Vec2Model``, whose fresh
+    initialisation has every such parameter at exactly 0 or 1.
     ``sharpen`` scales every matrix: >1 gives peakier posteriors so that a
     1e-4 tolerance on probabilities is discriminating.
     """
