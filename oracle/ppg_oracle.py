@@ -174,7 +174,8 @@ def num_layers(state):
     return n
 
 
-def window_forward(state, x, clens, is_causal=False, heads=2, quant=None):
+def window_forward(state, x, clens, is_causal=False, heads=2, quant=None, dtype=torch.float32,
+                   mask_hook=None):
     """One unchunked forward, reference transformer.py:65-81.
 
     x: (B, Cin, Tc) fp32; clens: (B,) ints (valid frames per item).
@@ -188,6 +189,10 @@ def window_forward(state, x, clens, is_causal=False, heads=2, quant=None):
     (in-conv output as the layer-0 operand), 'qkv', 'p' (softmax numerators),
     'ao', 'x1' / 'x2' (LayerNorm outputs as operands; the residual stays fp32),
     'h' -- for the error attribution of tools/precision_attribution.py.
+
+    ``dtype``: the arithmetic (float64 for the references of tests/attention_probe.py; `state`
+    and `x` must then be of that dtype).  ``mask_hook(bias, clens, is_causal) -> bias`` may
+    replace the additive attention mask (B, 1, query, key) -- the mask mutants of the same module.
     """
     q_ = quant if quant is not None else (lambda stage, tensor: tensor)
     B, _, Tc = x.shape
@@ -202,11 +207,13 @@ def window_forward(state, x, clens, is_causal=False, heads=2, quant=None):
     z = h.permute(0, 2, 1) + state['position.encoding'][:Tc, 0][None]   # (B,Tc,H)
     zop = q_('x0', z)                       # operand copy of the residual stream
 
-    bias = torch.zeros(B, 1, Tc, Tc)
+    bias = torch.zeros(B, 1, Tc, Tc, dtype=dtype)
     bias = bias.masked_fill(~mask[:, None, None, :], float('-inf'))
     if is_causal:
         causal = t[None, :] > t[:, None]                        # key > query
         bias = bias.masked_fill(causal[None, None], float('-inf'))
+    if mask_hook is not None:
+        bias = mask_hook(bias, clens, is_causal)
 
     for l in range(num_layers(state)):
         p = f'model.layers.{l}.'
@@ -246,27 +253,30 @@ def window_forward(state, x, clens, is_causal=False, heads=2, quant=None):
     return y * mask[:, None, :]
 
 
-def forward(state, features, lengths, is_causal=False, legacy_mode=False, quant=None):
+def forward(state, features, lengths, is_causal=False, legacy_mode=False, quant=None,
+            dtype=torch.float32, mask_hook=None):
     """reference Transformer.forward (transformer.py:45-81) -> logits (B,40,T)."""
-    features = features.to(torch.float)
+    features = features.to(dtype)
     T = features.shape[-1]
     if legacy_mode or T <= CHUNK_LENGTH:
-        return window_forward(state, features, lengths, is_causal, quant=quant)
+        return window_forward(state, features, lengths, is_causal, quant=quant, dtype=dtype,
+                              mask_hook=mask_hook)
     padded = torch.nn.functional.pad(
         features, (CHUNK_OVERLAP, 0), mode='replicate')
     outputs = []
     for w in plan_windows(T, lengths):
         split = padded[..., w['start']:w['start'] + w['Tc']]
-        out = window_forward(state, split, w['clens'], is_causal, quant=quant)
+        out = window_forward(state, split, w['clens'], is_causal, quant=quant, dtype=dtype,
+                             mask_hook=mask_hook)
         outputs.append(out[..., w['keep_lo']:w['keep_hi']])
     return torch.cat(outputs, dim=-1)
 
 
 def from_features(state, features, lengths, softmax=True, is_causal=False,
-                  legacy_mode=False, quant=None):
+                  legacy_mode=False, quant=None, dtype=torch.float32, mask_hook=None):
     """reference ppgs.from_features / infer (core.py:72-128, 551-596), fp32."""
     with torch.inference_mode():
-        logits = forward(state, features, lengths, is_causal, legacy_mode, quant)
+        logits = forward(state, features, lengths, is_causal, legacy_mode, quant, dtype, mask_hook)
         if softmax:
             return torch.softmax(logits, dim=1)
         return logits
