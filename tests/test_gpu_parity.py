@@ -16,6 +16,7 @@ Tolerances (stated here, per the north star):
     (measured 2.8e-3), argmax agreement 100 % at C2 size.
 * frontend: fp16 outputs bit-equal for >= 99.5 % of values, never more than
   1 fp16 ulp apart (a different FFT factorisation flips rare roundings).
+  Tonal and onset input, against float64: the criteria of tests/frontend_probe.py (test_gpu_frontend_probe.py).
 """
 import numpy as np
 import pytest
