@@ -461,6 +461,61 @@ int ppg_dtw(int device, const float* ppg_x, int frames_x, const float* ppg_y, in
             void* stream);
 
 /*
+ * Forced alignment of a PPG to the phoneme sequence the speaker was meant to say, with goodness-of-pronunciation
+ * scores, and the free-running counterpart (no counterpart in the reference, which takes phoneme timings from
+ * outside aligners; its only use of a PPG as a sequence is the argmax + unique_consecutive decode of
+ * ppgs/edit/core.py:74-95, which ppg_decode restates).
+ *
+ *   For one utterance: P (40, T) and phoneme indices s[0 .. N-1], 1 <= N <= T.
+ *   e[t, n] = logf(min(max(P[s[n], t], 1e-8), 1 - 1e-8))                  (the clamp of ppg_distance)
+ *   D[0, 0] = e[0, 0];  D[0, n > 0] = -inf
+ *   D[t, n] = e[t, n] + max(D[t-1, n], D[t-1, n-1]) in fp32, added in order of t.  The path advances (takes n-1)
+ *            only if D[t-1, n-1] > D[t-1, n]; a tie stays.  Comparisons only.
+ *   total = D[T-1, N-1]; the trace-back starts at (T-1, N-1).
+ *   starts[n] = the first frame of phoneme n; starts[0] = 0, starts[N] = T, strictly increasing.
+ *   score[n]  = the mean of e[t, n] over starts[n] <= t < starts[n+1], summed in frame order.
+ *   gop[n]    = the mean over the same frames of e[t, n] - max_q logf(clamp(P[q, t])): <= 0, and exactly 0 where the
+ *               target is the frame's maximum (the classic goodness of pronunciation).
+ *   Repeated adjacent phonemes are legal; their boundary is decided by the tie rule and the data.
+ *
+ * ppg_align:
+ *   ppg             : device fp32 (items, 40, frames), padded to the longest item; frames at or past an item's
+ *                     length are never read
+ *   lengths         : device int32[items], each in [1, frames]
+ *   phonemes        : device int32 (items, max_phonemes), indices 0 .. 39; entries at or past an item's
+ *                     phoneme_lengths are never read
+ *   phoneme_lengths : device int32[items], each in [1, min(max_phonemes, lengths[item])]
+ *   total           : device fp32[items]
+ *   starts          : device int32 (items, max_phonemes + 1): entries 0 .. N of item b are written
+ *   score, gop      : device fp32 (items, max_phonemes): entries 0 .. N-1 are written; gop may be NULL
+ *   workspace       : device memory, 16-byte aligned, at least ppg_align_workspace_bytes(items, frames,
+ *                     max_phonemes) bytes: the prepared frames (176 B per frame) and the direction bits (128 B per
+ *                     frame)
+ *   An item whose device-side lengths are impossible (N > T, N < 1, N > max_phonemes, T outside [1, frames], a
+ *   phoneme index outside 0 .. 39) gets total = NaN; its starts, score and gop are left untouched and nothing is
+ *   accessed out of range.
+ * ppg_decode:
+ *   per frame the phoneme with the largest posterior (the lowest index on ties, comparisons only), then runs of equal
+ *   labels: phonemes (items, frames) int32 holds the runs' labels, starts (items, frames + 1) int32 their first
+ *   frames with starts[runs] = T, runs int32[items] their number; the rest is left alone.  An item with a length
+ *   outside [1, frames] gets runs = 0 and nothing else.
+ * Kernel launches on `stream` only: no allocation, synchronisation or copy.  Calls with workspaces of their own may
+ * run concurrently on several streams.  Every result is a function of its own item alone: a batch equals its singles
+ * bit for bit.
+ * Limits: PPG_ALIGN_MAX_FRAMES frames, PPG_ALIGN_MAX_PHONEMES phonemes and PPG_ALIGN_MAX_ITEMS items per call
+ * (PPG_EINVAL above them; ppg_align_workspace_bytes, which is host-only, returns 0 for such arguments).
+ */
+#define PPG_ALIGN_MAX_FRAMES 4096
+#define PPG_ALIGN_MAX_PHONEMES 1024
+#define PPG_ALIGN_MAX_ITEMS 65535
+size_t ppg_align_workspace_bytes(int items, int frames, int max_phonemes);
+int ppg_align(int device, const float* ppg, int frames, int items, const int32_t* lengths,
+              const int32_t* phonemes, int max_phonemes, const int32_t* phoneme_lengths, float* total,
+              int32_t* starts, float* score, float* gop, void* workspace, size_t workspace_bytes, void* stream);
+int ppg_decode(int device, const float* ppg, int frames, int items, const int32_t* lengths, int32_t* phonemes,
+               int32_t* starts, int32_t* runs, void* stream);
+
+/*
  * Frame metrics accumulated on the device: what the reference's `python -m ppgs.evaluate` computes per batch with
  * five metric objects (ppgs/evaluate/metrics.py: Accuracy, CategoricalAccuracy, JensenShannon, TopKAccuracy, Loss,
  * DistanceMatrix), here ONE kernel launch per batch into one device block, no host synchronisation, read once at

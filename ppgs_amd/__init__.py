@@ -12,7 +12,7 @@ from .core import (                   # noqa: F401
     from_files_to_files, from_dataloader, infer, resample,
     distance, interpolate, sparsify,
     representation_file_extension, engine_for, clear_cache)
-from . import core, distributed, dtw, edit, evaluate      # noqa: F401
+from . import alignment, core, distributed, dtw, edit, evaluate      # noqa: F401
 from .engine import FrontendStream, audio_stream_frames   # noqa: F401
 
 __version__ = '0.1.0'

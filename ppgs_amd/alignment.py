@@ -1,0 +1,217 @@
+"""Forced alignment of a PPG to a phoneme sequence, with goodness-of-pronunciation scores.
+
+`ppgs_amd.distance` and `ppgs_amd.dtw` say how far apart two pronunciations are.  This module answers the other
+question of pronunciation work: given the PPG and the phonemes the speaker was meant to say, where does each phoneme
+start, and how well was it said?  It runs on the GPU (ppg_align and ppg_decode, ppgs_amd/csrc/ppg_align.hip).
+
+For one utterance, PPG P (40, T) and phoneme indices s of length N, 1 <= N <= T:
+
+    e[t, n] = logf(min(max(P[s[n], t], 1e-8), 1 - 1e-8))              (the clamp of `distance`)
+    D[0, 0] = e[0, 0];  D[0, n > 0] = -inf
+    D[t, n] = e[t, n] + max(D[t-1, n], D[t-1, n-1])                    (fp32, added in order of t)
+
+The path advances to the next phoneme only if D[t-1, n-1] > D[t-1, n]; a tie stays.  total = D[T-1, N-1], and the
+trace-back from (T-1, N-1) gives
+
+    starts (N + 1,) int32   starts[n] is the first frame of phoneme n; starts[0] = 0, starts[N] = T, strictly increasing
+    score  (N,) fp32        the mean of e[t, n] over the phoneme's frames, summed in frame order
+    gop    (N,) fp32        the mean over those frames of e[t, n] - max_q logf(clamp(P[q, t])): <= 0, and exactly 0
+                            where the target is every frame's most likely phoneme (goodness of pronunciation)
+
+Repeated adjacent phonemes are legal; their boundary is decided by the tie rule and the data.  There is no optional
+silence and no skipping: every phoneme of the sequence gets at least one frame.
+
+    alignment = ppgs_amd.alignment.forced(ppg, ['hh', 'ah', 'l', 'ow'])
+    for name, start, end, score, gop in ppgs_amd.alignment.segments(alignment): ...
+    free = ppgs_amd.alignment.decode(ppg)            # what the PPG says by itself: runs of the per-frame argmax
+"""
+import collections
+
+import torch
+
+from . import config, core, engine
+from .phonemes import PHONEMES, PHONEME_TO_INDEX_MAPPING
+
+MAX_FRAMES = engine.ALIGN_MAX_FRAMES
+MAX_PHONEMES = engine.ALIGN_MAX_PHONEMES
+
+Alignment = collections.namedtuple('Alignment', ['phonemes', 'starts', 'total', 'score', 'gop'])
+Decoding = collections.namedtuple('Decoding', ['phonemes', 'starts'])
+
+
+def _ppg(ppg):
+    """Shape checks of a PPG or a batch of them: (batched, batch, frames)."""
+    if not torch.is_tensor(ppg) or ppg.dim() not in (2, 3):
+        raise ValueError(f'PPG must be (40, frames) or (batch, 40, frames), got {tuple(getattr(ppg, "shape", ()))}')
+    if ppg.shape[-2] != config.OUTPUT_CHANNELS:
+        raise ValueError(f'PPG must have {config.OUTPUT_CHANNELS} channels, got {tuple(ppg.shape)}')
+    batched = ppg.dim() == 3
+    if batched and ppg.shape[0] < 1:
+        raise ValueError('empty batch')
+    frames = ppg.shape[-1]
+    if frames < 1:
+        raise ValueError(f'PPG must have at least one frame, got {tuple(ppg.shape)}')
+    if frames > MAX_FRAMES:
+        raise ValueError(f'alignment takes at most {MAX_FRAMES} frames, got {frames}')
+    return batched, ppg.shape[0] if batched else 1, frames
+
+
+def _lengths(lengths, batch, frames):
+    if lengths is None:
+        return [frames] * batch
+    if torch.is_tensor(lengths):
+        lengths = lengths.detach().cpu().reshape(-1).tolist()
+    elif isinstance(lengths, int):
+        lengths = [lengths]
+    lengths = [int(v) for v in lengths]
+    if len(lengths) != batch:
+        raise ValueError(f'lengths has {len(lengths)} entries for a batch of {batch}')
+    for value in lengths:
+        if not 1 <= value <= frames:
+            raise ValueError(f'lengths: {value} is outside [1, {frames}]')
+    return lengths
+
+
+def _sequence(phonemes):
+    """One phoneme sequence, as names or indices, as a list of checked indices."""
+    if torch.is_tensor(phonemes):
+        if phonemes.dim() != 1 or phonemes.is_floating_point() or phonemes.is_complex() or phonemes.dtype == torch.bool:
+            raise ValueError(f'a phoneme sequence must be a one-dimensional integer tensor, got {tuple(phonemes.shape)} '
+                             f'{phonemes.dtype}')
+        phonemes = phonemes.detach().cpu().tolist()
+    if isinstance(phonemes, (str, bytes)) or not isinstance(phonemes, (list, tuple)):
+        raise ValueError(f'a phoneme sequence must be a list of names or indices, got {type(phonemes).__name__}')
+    out = []
+    for value in phonemes:
+        if isinstance(value, str):
+            if value not in PHONEME_TO_INDEX_MAPPING:
+                raise ValueError(f'unknown phoneme {value!r}: the names are ppgs_amd.PHONEMES')
+            value = PHONEME_TO_INDEX_MAPPING[value]
+        elif isinstance(value, bool) or not isinstance(value, int):
+            raise ValueError(f'a phoneme must be a name or an index, got {value!r}')
+        if not 0 <= value < len(PHONEMES):
+            raise ValueError(f'phoneme index {value} is outside [0, {len(PHONEMES) - 1}]')
+        out.append(value)
+    return out
+
+
+def _sequences(phonemes, phoneme_lengths, batched, batch, lengths):
+    """The transcripts of a call as a list of index lists, one per item, each within its item's frames."""
+    if not batched:
+        if phoneme_lengths is not None:
+            raise ValueError('phoneme_lengths go with a batch: slice a single sequence instead')
+        sequences = [_sequence(phonemes)]
+    elif torch.is_tensor(phonemes) and phonemes.dim() == 2:
+        if phonemes.shape[0] != batch:
+            raise ValueError(f'phonemes has {phonemes.shape[0]} rows for a batch of {batch}')
+        if phonemes.is_floating_point() or phonemes.is_complex() or phonemes.dtype == torch.bool:
+            raise ValueError(f'a phoneme table must be an integer tensor, got {phonemes.dtype}')
+        if phoneme_lengths is None:
+            counts = [phonemes.shape[1]] * batch
+        else:
+            if torch.is_tensor(phoneme_lengths):
+                phoneme_lengths = phoneme_lengths.detach().cpu().reshape(-1).tolist()
+            counts = [int(v) for v in phoneme_lengths]
+            if len(counts) != batch:
+                raise ValueError(f'phoneme_lengths has {len(counts)} entries for a batch of {batch}')
+            for value in counts:
+                if not 0 <= value <= phonemes.shape[1]:
+                    raise ValueError(f'phoneme_lengths: {value} is outside [1, {phonemes.shape[1]}]')
+        # one copy to the host and one comparison for the whole table, not one per row
+        host = phonemes.detach().cpu().to(torch.int64)
+        used = torch.arange(host.shape[1])[None, :] < torch.tensor(counts)[:, None]
+        if bool(((host < 0) | (host >= len(PHONEMES)))[used].any()):
+            raise ValueError(f'a phoneme index is outside [0, {len(PHONEMES) - 1}]')
+        sequences = [row[:count] for row, count in zip(host.tolist(), counts)]
+    else:
+        if phoneme_lengths is not None:
+            raise ValueError('phoneme_lengths go with a padded (batch, N) tensor of phonemes')
+        if isinstance(phonemes, (str, bytes)) or not isinstance(phonemes, (list, tuple)) or len(phonemes) != batch:
+            raise ValueError(f'a batch of {batch} takes a list of {batch} phoneme sequences or a (batch, N) tensor')
+        sequences = [_sequence(item) for item in phonemes]
+    for sequence, frames in zip(sequences, lengths):
+        if len(sequence) < 1:
+            raise ValueError('an empty phoneme sequence cannot be aligned')
+        if len(sequence) > MAX_PHONEMES:
+            raise ValueError(f'alignment takes at most {MAX_PHONEMES} phonemes, got {len(sequence)}')
+        if len(sequence) > frames:
+            raise ValueError(f'{len(sequence)} phonemes do not fit {frames} frames: every phoneme takes a frame')
+    return sequences
+
+
+def forced(ppg, phonemes, lengths=None, phoneme_lengths=None, gop=True):
+    """Align `ppg` to the phonemes the speaker was meant to say: Alignment(phonemes, starts, total, score, gop).
+
+    `ppg` is (40, T) with `phonemes` a list of names from `ppgs_amd.PHONEMES` or of indices, or an integer tensor; or a
+    batch (B, 40, T) padded to the longest item with `lengths` per item (the padding is never read) and `phonemes` a
+    list of B such sequences, or a padded (B, Nmax) integer tensor with `phoneme_lengths`.  One utterance returns
+    device tensors: phonemes (N,) int32, starts (N + 1,) int32, total 0-d, score and gop (N,) fp32.  A batch returns
+    lists of B such tensors for the ragged fields and total (B,).  gop=False skips that sum and returns None for it.
+    A batch equals its single calls bit for bit."""
+    batched, batch, frames = _ppg(ppg)
+    if not batched and lengths is not None:
+        raise ValueError('lengths go with a batch: slice a single PPG instead')
+    lengths = _lengths(lengths, batch, frames)
+    sequences = _sequences(phonemes, phoneme_lengths, batched, batch, lengths)
+    counts = [len(sequence) for sequence in sequences]
+    most = max(counts)
+    device = core.device_for(None, ppg)
+    table = torch.tensor([sequence + [-1] * (most - len(sequence)) for sequence in sequences], dtype=torch.int32)
+    table = table.to(device)
+    x = ppg.to(device)
+    total, starts, score, below = engine.align_items(x if batched else x[None], lengths, table, counts, gop)
+    if not batched:
+        return Alignment(table[0], starts[0], total[0], score[0], below[0] if gop else None)
+    return Alignment(
+        [table[b, :n] for b, n in enumerate(counts)], [starts[b, :n + 1] for b, n in enumerate(counts)], total,
+        [score[b, :n] for b, n in enumerate(counts)], [below[b, :n] for b, n in enumerate(counts)] if gop else None)
+
+
+def decode(ppg, lengths=None):
+    """What the PPG says by itself: Decoding(phonemes, starts), the runs of the per-frame most likely phoneme (the
+    lowest index on ties, as torch.argmax) -- `torch.unique_consecutive(ppg.argmax(0))` with the runs' first frames.
+
+    (40, T) returns device tensors phonemes (R,) int32 and starts (R + 1,) int32 with starts[R] = T; a batch
+    (B, 40, T) with `lengths` returns lists of B such tensors.  `forced(ppg, decode(ppg).phonemes)` reproduces these
+    starts wherever every frame's best phoneme is clear of the others."""
+    batched, batch, frames = _ppg(ppg)
+    if not batched and lengths is not None:
+        raise ValueError('lengths go with a batch: slice a single PPG instead')
+    lengths = _lengths(lengths, batch, frames)
+    device = core.device_for(None, ppg)
+    x = ppg.to(device)
+    phonemes, starts, runs = engine.decode_items(x if batched else x[None], lengths)
+    runs = runs.tolist()
+    if not batched:
+        return Decoding(phonemes[0, :runs[0]], starts[0, :runs[0] + 1])
+    return Decoding([phonemes[b, :r] for b, r in enumerate(runs)], [starts[b, :r + 1] for b, r in enumerate(runs)])
+
+
+def segments(alignment, sample_rate=config.SAMPLE_RATE, hopsize=config.HOPSIZE):
+    """An alignment (or a decoding) of one utterance as a host list of (phoneme name, start seconds, end seconds,
+    score, gop), one per phoneme; a batch gives a list of such lists.  Fields the input lacks are None."""
+    phonemes, starts = alignment.phonemes, alignment.starts
+    score, gop = getattr(alignment, 'score', None), getattr(alignment, 'gop', None)
+    if isinstance(phonemes, (list, tuple)):
+        return [segments(Alignment(phonemes[b], starts[b], None, None if score is None else score[b],
+                                   None if gop is None else gop[b]), sample_rate, hopsize)
+                for b in range(len(phonemes))]
+    names = [PHONEMES[index] for index in phonemes.tolist()]
+    edges = [frame * hopsize / sample_rate for frame in starts.tolist()]
+    if len(edges) != len(names) + 1:
+        raise ValueError(f'{len(names)} phonemes take {len(names) + 1} starts, got {len(edges)}')
+    score = [None] * len(names) if score is None else score.tolist()
+    gop = [None] * len(names) if gop is None else gop.tolist()
+    return [(name, edges[n], edges[n + 1], score[n], gop[n]) for n, name in enumerate(names)]
+
+
+def frame_labels(starts, phonemes, frames):
+    """An alignment expanded to one label per frame: (frames,) with phonemes[n] at starts[n] <= t < starts[n + 1].
+    Plain tensor arithmetic: works on CPU and device tensors alike."""
+    if starts.dim() != 1 or phonemes.dim() != 1 or starts.shape[0] != phonemes.shape[0] + 1 or phonemes.shape[0] < 1:
+        raise ValueError(f'N >= 1 phonemes take N + 1 starts, got {tuple(phonemes.shape)} and {tuple(starts.shape)}')
+    if frames < 1:
+        raise ValueError(f'frames must be positive, got {frames}')
+    inner = starts[1:-1].to(torch.int64).contiguous()           # the N - 1 boundaries inside the utterance
+    time = torch.arange(frames, dtype=torch.int64, device=starts.device)
+    return phonemes.to(starts.device)[torch.bucketize(time, inner, right=True)]

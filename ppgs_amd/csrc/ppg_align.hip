@@ -1,0 +1,374 @@
+// Forced alignment of a PPG to a phoneme sequence with goodness-of-pronunciation scores, and the free-running
+// run-length decode, on the device.
+//
+//   e[t, n] = logf(min(max(P[s[n], t], 1e-8), 1 - 1e-8))                      (the clamp of ppg_distance)
+//   D[0, 0] = e[0, 0];  D[0, n > 0] = -inf
+//   D[t, n] = e[t, n] + max(D[t-1, n], D[t-1, n-1])                            (fp32, added in order of t)
+//   the path advances (takes n-1) only if D[t-1, n-1] > D[t-1, n]; a tie stays.  Comparisons only.
+//   total = D[T-1, N-1]; the trace-back starts at (T-1, N-1).
+//
+// Five kernels, all on the caller's stream, no allocation, no synchronisation:
+//   align_prepare    one thread per frame: the 40 clamped log-posteriors and their maximum, frame-major (176 B per
+//                    frame).  ONE piece of code for every consumer, so a frame always gives the same bits.
+//   align_programme  one wave per utterance.  Lane l keeps a strip of S consecutive states (their phoneme and
+//                    D[., n]) in registers, S = 1, 4 or 16 by the utterance's own N, and takes the state below its
+//                    strip from lane l - 1 by a cross-lane move.  Time is the serial loop; there is no skew, every
+//                    state of frame t needs frame t-1 only.  Emissions are a gather from a chunk of prepared frames
+//                    in LDS; the next chunk is in flight while the current one is consumed.  One direction bit per
+//                    cell: a 16-bit word per lane and frame.
+//   align_traceback  one wave per utterance: direction rows come through LDS 64 frames at a time, the walk itself is
+//                    wave-uniform.
+//   align_score      one thread per (utterance, phoneme): its segment summed in frame order.
+//   decode_runs      one wave per utterance: per-frame argmax (lowest index on ties), run boundaries compacted with
+//                    ballot and a popcount prefix.
+#include "../../include/ppgs_amd.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+namespace ppg {
+int fail_message(int code, const char* fmt, ...);
+}
+
+namespace {
+
+constexpr int NP = 40;                        // phonemes
+constexpr int PREP = 44;                      // floats per prepared frame: 40 log-posteriors, their maximum, 3 zeros
+constexpr int PREP_VEC = PREP / 4;            // ... as 16-byte pieces
+constexpr int CHUNK = 32;                     // frames staged in LDS at a time
+constexpr int CHUNK_VEC = CHUNK * PREP_VEC;   // 352 pieces = 5.5 KiB
+constexpr int FETCH = (CHUNK_VEC + 63) / 64;  // pieces per lane and chunk
+constexpr int ROW = 64;                       // direction words (16 bit) per frame: one per lane
+constexpr int ROW_VEC = ROW * 2 / 16;         // a direction row as 16-byte pieces
+constexpr int WALK = 64;                      // frames per LDS refill of the trace-back
+
+struct Layout {
+    size_t logp, dirs, bytes;                 // byte offsets into the workspace
+};
+
+inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
+
+inline Layout layout(int items, int frames) {
+    Layout w{};
+    size_t at = 0;
+    w.logp = at; at = align256(at + (size_t)items * frames * PREP * sizeof(float));
+    w.dirs = at; at = align256(at + (size_t)items * frames * ROW * sizeof(uint16_t));
+    w.bytes = at;
+    return w;
+}
+
+// strip length of an utterance with n phonemes: 64 lanes x S states cover it
+__host__ __device__ inline int strip_shift(int n) { return n <= 64 ? 0 : n <= 256 ? 2 : 4; }
+
+// the lengths an utterance may have; everything else yields total = NaN and touches nothing
+__device__ __forceinline__ bool plausible(int t, int n, int frames, int max_phonemes) {
+    return t >= 1 && t <= frames && n >= 1 && n <= max_phonemes && n <= t;
+}
+
+// grid (ceil(frames / 64), items), 64 threads: thread = frame.  src (items, 40, frames); only t < lengths[item] is read
+__global__ __launch_bounds__(64) void align_prepare(const float* __restrict__ ppg, int frames,
+                                                     const int* __restrict__ lengths, float* __restrict__ logp)
+{
+    const int item = blockIdx.y;
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= frames || t >= lengths[item]) return;
+    const float* src = ppg + (size_t)item * NP * frames + t;
+    float4* dst = reinterpret_cast<float4*>(logp + ((size_t)item * frames + t) * PREP);
+    float v[PREP];
+    float top = -INFINITY;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        v[p] = logf(fminf(fmaxf(src[(size_t)p * frames], 1e-8f), 1.f - 1e-8f));
+        top = fmaxf(top, v[p]);
+    }
+    v[NP] = top;
+    v[NP + 1] = v[NP + 2] = v[NP + 3] = 0.f;
+#pragma unroll
+    for (int q = 0; q < PREP_VEC; ++q) dst[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+}
+
+// lane l <- lane l - 1; lane 0 <- first.  Call it from wave-uniform control flow only.
+__device__ __forceinline__ float lane_up(float v, float first) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(first), __float_as_int(v), 0x138 /* wave_shr:1 */,
+                                                      0xf, 0xf, false));
+}
+
+// the prepared frames t0 .. t0 + CHUNK - 1 of one utterance, those below T only, one 16-byte piece per lane and u
+__device__ __forceinline__ void fetch(const float4* __restrict__ src, int t0, int T, int lane, float4 (&piece)[FETCH]) {
+    const int pieces = min(CHUNK, T - t0) * PREP_VEC;          // <= 0 past the end: nothing is read
+#pragma unroll
+    for (int u = 0; u < FETCH; ++u) {
+        const int idx = u * 64 + lane;
+        piece[u] = idx < pieces ? src[(size_t)t0 * PREP_VEC + idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+__device__ __forceinline__ void stash(float4* __restrict__ stage, int lane, const float4 (&piece)[FETCH]) {
+#pragma unroll
+    for (int u = 0; u < FETCH; ++u) {
+        const int idx = u * 64 + lane;
+        if (idx < CHUNK_VEC) stage[idx] = piece[u];
+    }
+}
+
+// The programme of one utterance with S states per lane.  Everything here is wave-uniform control flow.
+template <int S>
+__device__ __forceinline__ float programme(const float4* __restrict__ src, int T, int N, const int* __restrict__ sym,
+                                           uint16_t* __restrict__ dirs, float4 (&stage)[2][CHUNK_VEC], int lane)
+{
+    int s[S]; float d[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        const int n = lane * S + k;
+        s[k] = n < N ? sym[n] : 0;                             // states at or above N run along on phoneme 0, unread
+        d[k] = -INFINITY;
+    }
+    float4 next[FETCH];
+    fetch(src, 0, T, lane, next);
+    stash(stage[0], lane, next);
+    __syncthreads();
+    int buf = 0;
+    for (int t0 = 0; t0 < T; t0 += CHUNK, buf ^= 1) {
+        fetch(src, t0 + CHUNK, T, lane, next);                 // in flight while this chunk is consumed
+        const float* e = reinterpret_cast<const float*>(stage[buf]);
+        const int count = min(CHUNK, T - t0);
+        float cur[S];                                          // frame t's emissions, read one frame ahead of their use
+#pragma unroll
+        for (int k = 0; k < S; ++k) cur[k] = e[s[k]];
+        for (int u = 0; u < count; ++u) {
+            const int t = t0 + u;
+            const float* ahead = e + min(u + 1, CHUNK - 1) * PREP;       // (the last one re-reads a row: unused)
+            float coming[S];
+#pragma unroll
+            for (int k = 0; k < S; ++k) coming[k] = ahead[s[k]];
+            // the state below the strip; for the very first cell the virtual origin D[-1, -1] = 0, so D[0, 0] = e + 0
+            const float below = lane_up(d[S - 1], t == 0 ? 0.f : -INFINITY);
+            uint32_t bits = 0;
+#pragma unroll
+            for (int k = S - 1; k >= 0; --k) {                 // downwards: d[k - 1] is still frame t-1's
+                const float stay = d[k], from = k ? d[k - 1] : below;
+                const bool advance = from > stay;
+                d[k] = cur[k] + (advance ? from : stay);       // -inf + finite = -inf: never NaN
+                bits |= (uint32_t)advance << k;
+            }
+            dirs[(size_t)t * ROW + lane] = (uint16_t)bits;
+#pragma unroll
+            for (int k = 0; k < S; ++k) cur[k] = coming[k];
+        }
+        stash(stage[buf ^ 1], lane, next);
+        __syncthreads();
+    }
+    const int k = (N - 1) % S;
+    float last = d[0];
+#pragma unroll
+    for (int q = 1; q < S; ++q) last = k == q ? d[q] : last;
+    return last;                                               // meaningful in lane (N - 1) / S
+}
+
+// grid (items), 64 threads
+__global__ __launch_bounds__(64) void align_programme(const float* __restrict__ logp, int frames,
+                                                       const int* __restrict__ lengths,
+                                                       const int* __restrict__ phonemes, int max_phonemes,
+                                                       const int* __restrict__ phoneme_lengths,
+                                                       uint16_t* __restrict__ dirs, float* __restrict__ total)
+{
+    __shared__ float4 stage[2][CHUNK_VEC];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item], N = phoneme_lengths[item];
+    const int* sym = phonemes + (size_t)item * max_phonemes;
+    bool fine = plausible(T, N, frames, max_phonemes);
+    if (fine) {
+        bool bad = false;
+        for (int n = lane; n < N; n += 64) bad |= (unsigned)sym[n] >= (unsigned)NP;
+        fine = !__any(bad);
+    }
+    if (!fine) {                                               // (uniform)
+        if (lane == 0) total[item] = NAN;
+        return;
+    }
+    const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
+    uint16_t* out = dirs + (size_t)item * frames * ROW;
+    const int shift = strip_shift(N);
+    float last;
+    if (shift == 0) last = programme<1>(src, T, N, sym, out, stage, lane);
+    else if (shift == 2) last = programme<4>(src, T, N, sym, out, stage, lane);
+    else last = programme<16>(src, T, N, sym, out, stage, lane);
+    if (lane == (N - 1) >> shift) total[item] = last;
+}
+
+// grid (items), 64 threads.  An utterance whose total is NaN was refused by the programme: starts stay untouched.
+__global__ __launch_bounds__(64) void align_traceback(const uint16_t* __restrict__ dirs, int frames,
+                                                       const int* __restrict__ lengths, int max_phonemes,
+                                                       const int* __restrict__ phoneme_lengths,
+                                                       const float* __restrict__ total, int* __restrict__ starts)
+{
+    __shared__ uint4 rows[WALK * ROW_VEC];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item], N = phoneme_lengths[item];
+    if (!plausible(T, N, frames, max_phonemes) || total[item] != total[item]) return;
+    const int shift = strip_shift(N), mask = (1 << shift) - 1;
+    const uint4* src = reinterpret_cast<const uint4*>(dirs + (size_t)item * frames * ROW);
+    int* out = starts + (size_t)item * (max_phonemes + 1);
+    uint4 next[ROW_VEC];
+    auto load = [&](int c) {                                   // rows of frames c * WALK ..., those below T only
+        const int pieces = min(WALK, T - c * WALK) * ROW_VEC;
+#pragma unroll
+        for (int u = 0; u < ROW_VEC; ++u) {
+            const int idx = u * 64 + lane;
+            next[u] = idx < pieces ? src[(size_t)c * WALK * ROW_VEC + idx] : make_uint4(0, 0, 0, 0);
+        }
+    };
+    int n = N - 1;
+    int c = (T - 1) / WALK;
+    load(c);
+    for (; c >= 0; --c) {
+        __syncthreads();                                       // the walk over the previous refill is over
+#pragma unroll
+        for (int u = 0; u < ROW_VEC; ++u) rows[u * 64 + lane] = next[u];
+        __syncthreads();
+        if (c > 0) load(c - 1);
+        const uint16_t* row = reinterpret_cast<const uint16_t*>(rows);
+        const int low = max(c * WALK, 1);
+        for (int t = min(T - 1, c * WALK + WALK - 1); t >= low; --t) {
+            const uint32_t word = row[(t & (WALK - 1)) * ROW + (n >> shift)];      // the same address in every lane
+            if (n > 0 && ((word >> (n & mask)) & 1)) {
+                if (lane == 0) out[n] = t;
+                --n;
+            }
+        }
+    }
+    if (lane == 0) { out[0] = 0; out[N] = T; }
+}
+
+// grid (ceil(max_phonemes / 64), items), 64 threads: thread = phoneme
+__global__ __launch_bounds__(64) void align_score(const float* __restrict__ logp, int frames,
+                                                   const int* __restrict__ lengths,
+                                                   const int* __restrict__ phonemes, int max_phonemes,
+                                                   const int* __restrict__ phoneme_lengths,
+                                                   const float* __restrict__ total, const int* __restrict__ starts,
+                                                   float* __restrict__ score, float* __restrict__ gop)
+{
+    const int item = blockIdx.y, n = blockIdx.x * 64 + threadIdx.x;
+    const int T = lengths[item], N = phoneme_lengths[item];
+    if (!plausible(T, N, frames, max_phonemes) || total[item] != total[item] || n >= N) return;
+    const int* bounds = starts + (size_t)item * (max_phonemes + 1) + n;
+    const int first = max(bounds[0], 0), end = min(bounds[1], T);
+    const float* row = logp + (size_t)item * frames * PREP + phonemes[(size_t)item * max_phonemes + n];
+    const float* top = logp + (size_t)item * frames * PREP + NP;
+    float sum = 0.f, below = 0.f;
+    for (int t = first; t < end; ++t) {
+        const float e = row[(size_t)t * PREP];
+        sum += e;
+        if (gop) below += e - top[(size_t)t * PREP];           // exactly 0 where the target is the frame's maximum
+    }
+    const float count = (float)(end - first);
+    score[(size_t)item * max_phonemes + n] = sum / count;
+    if (gop) gop[(size_t)item * max_phonemes + n] = below / count;
+}
+
+// grid (items), 64 threads: lane = frame of the current 64
+__global__ __launch_bounds__(64) void decode_runs(const float* __restrict__ ppg, int frames,
+                                                   const int* __restrict__ lengths, int* __restrict__ phonemes,
+                                                   int* __restrict__ starts, int* __restrict__ runs)
+{
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item];
+    if (T < 1 || T > frames) {                                 // (uniform)
+        if (lane == 0) runs[item] = 0;
+        return;
+    }
+    const float* src = ppg + (size_t)item * NP * frames;
+    int* out_phonemes = phonemes + (size_t)item * frames;
+    int* out_starts = starts + (size_t)item * (frames + 1);
+    int carry = -1, base = 0;                                  // the label before this chunk; runs so far
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        int label = -2;
+        if (t < T) {
+            float best = src[t];
+            label = 0;
+#pragma unroll 8
+            for (int p = 1; p < NP; ++p) {
+                const float v = src[(size_t)p * frames + t];
+                if (v > best) { best = v; label = p; }         // the lowest index on ties
+            }
+        }
+        const int before = __builtin_amdgcn_update_dpp(carry, label, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+        const bool opens = t < T && label != before;
+        const unsigned long long mask = __ballot(opens);
+        if (opens) {
+            const int at = base + __popcll(mask & ((1ull << lane) - 1ull));
+            out_phonemes[at] = label;
+            out_starts[at] = t;
+        }
+        base += __popcll(mask);
+        carry = __builtin_amdgcn_readlane(label, 63);
+    }
+    if (lane == 0) { runs[item] = base; out_starts[base] = T; }
+}
+
+int check_common(const char* what, const void* ppg, int frames, int items, const void* lengths) {
+    if (!ppg || !lengths || items <= 0 || frames <= 0) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (frames > PPG_ALIGN_MAX_FRAMES)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d frames, at most %d", what, frames, PPG_ALIGN_MAX_FRAMES);
+    if (items > PPG_ALIGN_MAX_ITEMS)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d items, at most %d per call", what, items, PPG_ALIGN_MAX_ITEMS);
+    return PPG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ppg_align_workspace_bytes(int items, int frames, int max_phonemes) {
+    if (items <= 0 || items > PPG_ALIGN_MAX_ITEMS || frames <= 0 || frames > PPG_ALIGN_MAX_FRAMES ||
+        max_phonemes <= 0 || max_phonemes > PPG_ALIGN_MAX_PHONEMES)
+        return 0;
+    return layout(items, frames).bytes;
+}
+
+int ppg_align(int device, const float* ppg, int frames, int items, const int32_t* lengths, const int32_t* phonemes,
+              int max_phonemes, const int32_t* phoneme_lengths, float* total, int32_t* starts, float* score,
+              float* gop, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = check_common("align", ppg, frames, items, lengths)) return rc;
+    if (!phonemes || !phoneme_lengths || !total || !starts || !score || !workspace || max_phonemes <= 0)
+        return ppg::fail_message(PPG_EINVAL, "align: bad argument");
+    if (max_phonemes > PPG_ALIGN_MAX_PHONEMES)
+        return ppg::fail_message(PPG_EINVAL, "align: %d phonemes, at most %d", max_phonemes, PPG_ALIGN_MAX_PHONEMES);
+    const Layout w = layout(items, frames);
+    if (workspace_bytes < w.bytes)
+        return ppg::fail_message(PPG_EINVAL, "align: workspace of %zu bytes, %zu needed", workspace_bytes, w.bytes);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16)
+        return ppg::fail_message(PPG_EINVAL, "align: workspace must be 16-byte aligned");
+    if (hipSetDevice(device) != hipSuccess)
+        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    float* logp = reinterpret_cast<float*>(ws + w.logp);
+    uint16_t* dirs = reinterpret_cast<uint16_t*>(ws + w.dirs);
+    hipLaunchKernelGGL(align_prepare, dim3((frames + 63) / 64, items), dim3(64), 0, s, ppg, frames, lengths, logp);
+    hipLaunchKernelGGL(align_programme, dim3(items), dim3(64), 0, s, logp, frames, lengths, phonemes, max_phonemes,
+                       phoneme_lengths, dirs, total);
+    hipLaunchKernelGGL(align_traceback, dim3(items), dim3(64), 0, s, dirs, frames, lengths, max_phonemes,
+                       phoneme_lengths, total, starts);
+    hipLaunchKernelGGL(align_score, dim3((max_phonemes + 63) / 64, items), dim3(64), 0, s, logp, frames, lengths,
+                       phonemes, max_phonemes, phoneme_lengths, total, starts, score, gop);
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "align: %s", hipGetErrorString(he));
+}
+
+int ppg_decode(int device, const float* ppg, int frames, int items, const int32_t* lengths, int32_t* phonemes,
+               int32_t* starts, int32_t* runs, void* stream) {
+    if (const int rc = check_common("decode", ppg, frames, items, lengths)) return rc;
+    if (!phonemes || !starts || !runs) return ppg::fail_message(PPG_EINVAL, "decode: bad argument");
+    if (hipSetDevice(device) != hipSuccess)
+        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    hipLaunchKernelGGL(decode_runs, dim3(items), dim3(64), 0, static_cast<hipStream_t>(stream), ppg, frames, lengths,
+                       phonemes, starts, runs);
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "decode: %s", hipGetErrorString(he));
+}
+
+}  // extern "C"

@@ -148,6 +148,14 @@ SYMBOLS = {
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'ppg_align_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_align': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_size_t, ctypes.c_void_p]),
+    'ppg_decode': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_metrics_state_bytes': (ctypes.c_size_t, []),
     'ppg_metrics_reset': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_metrics_update': (ctypes.c_int, [
@@ -689,6 +697,82 @@ def dtw_pairs(ppg_x, ppg_y, lengths_x, lengths_y, mix=None, want_path=False, wan
                 cost[at:].data_ptr() if want_cost else None,
                 workspace.data_ptr(), size, stream))
     return total, steps, path, cost
+
+
+ALIGN_MAX_FRAMES = 4096          # PPG_ALIGN_MAX_FRAMES
+ALIGN_MAX_PHONEMES = 1024        # PPG_ALIGN_MAX_PHONEMES
+ALIGN_MAX_ITEMS = 65535          # PPG_ALIGN_MAX_ITEMS, per call of the library
+ALIGN_WORKSPACE_BYTES = 1 << 30  # a larger batch runs as several calls, each within this much workspace
+
+
+def _items(ppg, lengths, what):
+    """The checks and conversions align_items and decode_items share: (x, lengths on the device as int32)."""
+    if not ppg.is_cuda:
+        raise PpgError('ppgs_amd: the post-ops work on HIP device tensors')
+    x = ppg.to(torch.float32).contiguous()
+    if x.dim() != 3 or x.shape[1] != 40 or x.shape[0] < 1:
+        raise ValueError(f'PPGs must be (items >= 1, 40, frames), got {tuple(x.shape)}')
+    if not 1 <= x.shape[2] <= ALIGN_MAX_FRAMES:
+        raise ValueError(f'{what} takes 1 to {ALIGN_MAX_FRAMES} frames, got {x.shape[2]}')
+    lengths = [int(v) for v in lengths]
+    if len(lengths) != x.shape[0]:
+        raise ValueError(f'{len(lengths)} lengths for {x.shape[0]} items')
+    return x, lengths
+
+
+def align_items(ppg, lengths, phonemes, phoneme_lengths, want_gop=True):
+    """Forced alignment of item b = ppg[b, :, :lengths[b]] to phonemes[b, :phoneme_lengths[b]] (ppg_align):
+    (items, 40, frames) on a GPU, phonemes a padded (items, max_phonemes) integer tensor, both lengths as host
+    integers -> total (items,) fp32, starts (items, max_phonemes + 1) int32, score and gop (items, max_phonemes) fp32
+    (gop None without want_gop).  Entries past an item's own N (N + 1 for starts) are zero."""
+    x, lengths = _items(ppg, lengths, 'align')
+    items, frames = x.shape[0], x.shape[2]
+    device = x.device
+    if phonemes.dim() != 2 or phonemes.shape[0] != items or not 1 <= phonemes.shape[1] <= ALIGN_MAX_PHONEMES:
+        raise ValueError(
+            f'phonemes must be ({items}, 1 to {ALIGN_MAX_PHONEMES}) for {items} items, got {tuple(phonemes.shape)}')
+    table = phonemes.to(device=device, dtype=torch.int32).contiguous()
+    most = table.shape[1]
+    phoneme_lengths = [int(v) for v in phoneme_lengths]
+    if len(phoneme_lengths) != items:
+        raise ValueError(f'{len(phoneme_lengths)} phoneme lengths for {items} items')
+    both = torch.tensor([lengths, phoneme_lengths], dtype=torch.int32).to(device)
+    total = torch.empty((items,), dtype=torch.float32, device=device)
+    starts = torch.zeros((items, most + 1), dtype=torch.int32, device=device)
+    score = torch.zeros((items, most), dtype=torch.float32, device=device)
+    gop = torch.zeros((items, most), dtype=torch.float32, device=device) if want_gop else None
+    lib = library()
+    group = max(1, min(items, ALIGN_MAX_ITEMS, ALIGN_WORKSPACE_BYTES // lib.ppg_align_workspace_bytes(1, frames, most)))
+    size = lib.ppg_align_workspace_bytes(group, frames, most)
+    workspace = torch.empty((size,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for at in range(0, items, group):
+            _check(lib.ppg_align(
+                device.index, x[at:].data_ptr(), frames, min(group, items - at), both[0, at:].data_ptr(),
+                table[at:].data_ptr(), most, both[1, at:].data_ptr(), total[at:].data_ptr(), starts[at:].data_ptr(),
+                score[at:].data_ptr(), gop[at:].data_ptr() if want_gop else None, workspace.data_ptr(), size, stream))
+    return total, starts, score, gop
+
+
+def decode_items(ppg, lengths):
+    """Run-length decode of item b = ppg[b, :, :lengths[b]] (ppg_decode): per frame the phoneme with the largest
+    posterior, then runs of equal labels -> phonemes (items, frames) int32, starts (items, frames + 1) int32 and
+    runs (items,) int32; entries past an item's runs (runs + 1 for starts) are zero."""
+    x, lengths = _items(ppg, lengths, 'decode')
+    items, frames = x.shape[0], x.shape[2]
+    device = x.device
+    lengths = torch.tensor(lengths, dtype=torch.int32).to(device)
+    phonemes = torch.zeros((items, frames), dtype=torch.int32, device=device)
+    starts = torch.zeros((items, frames + 1), dtype=torch.int32, device=device)
+    runs = torch.empty((items,), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for at in range(0, items, ALIGN_MAX_ITEMS):
+            _check(library().ppg_decode(
+                device.index, x[at:].data_ptr(), frames, min(ALIGN_MAX_ITEMS, items - at), lengths[at:].data_ptr(),
+                phonemes[at:].data_ptr(), starts[at:].data_ptr(), runs[at:].data_ptr(), stream))
+    return phonemes, starts, runs
 
 
 METRICS_FIXED_POINT = 2.0 ** 32        # the real-valued accumulators of PpgMetricsState count units of 2^-32
