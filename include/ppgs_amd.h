@@ -516,6 +516,42 @@ int ppg_decode(int device, const float* ppg, int frames, int items, const int32_
                int32_t* starts, int32_t* runs, void* stream);
 
 /*
+ * Forced alignment with optional phonemes: ppg_align for transcripts in which some phonemes may be left out -- the
+ * pauses a speaker may or may not make between words, a final consonant that may be dropped.  Not in the reference.
+ *
+ * Per utterance: P (40, T), phoneme indices s[0 .. N-1], flags opt[0 .. N-1] (non-zero: phoneme n may be left out).
+ * Emissions e[t, n] are those of ppg_align, bit for bit.  State -1 (a virtual origin) holds 0 before frame 0, every
+ * real state -inf.
+ *   stay = D[t-1, n];  adv = D[t-1, n-1];  skp = opt[n-1] ? D[t-1, n-2] : -inf   (a jump over the optional phoneme n-1)
+ *   D[t, n] = e[t, n] + best in fp32, added in order of t; best is stay, adv if adv > best, skp if skp > best, in that
+ *            order: stay beats advance beats skip on ties.  Comparisons only.
+ *   So D[0, 0] = e[0, 0], and D[0, 1] = e[0, 1] if opt[0].
+ *   The end is state N-1, or N-2 if opt[N-1] and D[T-1, N-2] > D[T-1, N-1]; total is D[T-1, end].
+ *   starts[0] = 0, starts[N] = T, non-decreasing; starts[n] == starts[n+1] exactly for the phonemes left out, whose
+ *   score and gop are NaN (0 / 0).  score and gop of the others are as in ppg_align.
+ * A legal transcript has no two adjacent optional phonemes (a jump passes over exactly one phoneme), at least one
+ * mandatory phoneme, and at most T mandatory ones.  N > T is legal within that.  With every flag zero the results are
+ * those of ppg_align bit for bit.
+ *
+ * ppg_align_optional: the arguments of ppg_align, and
+ *   optional        : device int32 (items, max_phonemes), the shape of `phonemes`; zero means mandatory; entries at or
+ *                     past an item's phoneme_lengths are never read
+ *   phoneme_lengths : device int32[items], each in [1, max_phonemes]
+ *   workspace       : device memory, 16-byte aligned, at least ppg_align_optional_workspace_bytes(items, frames,
+ *                     max_phonemes) bytes: the prepared frames (176 B per frame), two planes of direction bits
+ *                     (2 x 128 B per frame) and the end state of every item
+ *   An item that cannot be aligned (an illegal transcript as above, N < 1, N > max_phonemes, T outside [1, frames], a
+ *   phoneme index outside 0 .. 39) gets total = NaN; its starts, score and gop are left untouched and nothing is
+ *   accessed out of range.
+ * Launches, streams, limits, the argument checks and the error codes are those of ppg_align; an error launches nothing.
+ */
+size_t ppg_align_optional_workspace_bytes(int items, int frames, int max_phonemes);
+int ppg_align_optional(int device, const float* ppg, int frames, int items, const int32_t* lengths,
+                       const int32_t* phonemes, const int32_t* optional, int max_phonemes,
+                       const int32_t* phoneme_lengths, float* total, int32_t* starts, float* score, float* gop,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Frame metrics accumulated on the device: what the reference's `python -m ppgs.evaluate` computes per batch with
  * five metric objects (ppgs/evaluate/metrics.py: Accuracy, CategoricalAccuracy, JensenShannon, TopKAccuracy, Loss,
  * DistanceMatrix), here ONE kernel launch per batch into one device block, no host synchronisation, read once at

@@ -18,14 +18,31 @@ trace-back from (T-1, N-1) gives
     gop    (N,) fp32        the mean over those frames of e[t, n] - max_q logf(clamp(P[q, t])): <= 0, and exactly 0
                             where the target is every frame's most likely phoneme (goodness of pronunciation)
 
-Repeated adjacent phonemes are legal; their boundary is decided by the tie rule and the data.  There is no optional
-silence and no skipping: every phoneme of the sequence gets at least one frame.
+Repeated adjacent phonemes are legal; their boundary is decided by the tie rule and the data.  Without `optional`
+every phoneme of the sequence gets at least one frame.
 
     alignment = ppgs_amd.alignment.forced(ppg, ['hh', 'ah', 'l', 'ow'])
     for name, start, end, score, gop in ppgs_amd.alignment.segments(alignment): ...
     free = ppgs_amd.alignment.decode(ppg)            # what the PPG says by itself: runs of the per-frame argmax
+
+Optional phonemes (`forced(..., optional=flags)`, ppg_align_optional): a speaker pauses between words wherever they
+like, and drops a final consonant or a schwa.  flags[n] lets the path leave phoneme n out:
+
+    state -1, a virtual origin, holds 0 before frame 0; every real state holds -inf
+    D[t, n] = e[t, n] + the best of   stay D[t-1, n],   advance D[t-1, n-1],   skip D[t-1, n-2] if flags[n-1]
+
+taken in that order by strict comparisons, so stay beats advance beats skip on ties.  The end is state N-1, or N-2
+if flags[N-1] and D[T-1, N-2] > D[T-1, N-1].  A phoneme that was left out has starts[n] == starts[n+1] (starts is
+non-decreasing then) and NaN for its score and gop; the others are scored as before.  No two adjacent phonemes may be
+optional, at least one must be mandatory, and the mandatory ones must fit the frames; N may exceed T within that.
+With every flag False the results are those of the plain alignment bit for bit.
+
+    phonemes, optional, word_of = ppgs_amd.alignment.transcript([['hh', 'ah'], ['l', 'ow']])   # <silent> around words
+    alignment = ppgs_amd.alignment.forced(ppg, phonemes, optional=optional)
+    for word, start, end, gop in ppgs_amd.alignment.word_segments(alignment, word_of): ...
 """
 import collections
+import math
 
 import torch
 
@@ -95,8 +112,8 @@ def _sequence(phonemes):
     return out
 
 
-def _sequences(phonemes, phoneme_lengths, batched, batch, lengths):
-    """The transcripts of a call as a list of index lists, one per item, each within its item's frames."""
+def _sequences(phonemes, phoneme_lengths, batched, batch, lengths, fit=True):
+    """The transcripts of a call as a list of index lists, one per item, each within its item's frames (`fit`)."""
     if not batched:
         if phoneme_lengths is not None:
             raise ValueError('phoneme_lengths go with a batch: slice a single sequence instead')
@@ -134,12 +151,59 @@ def _sequences(phonemes, phoneme_lengths, batched, batch, lengths):
             raise ValueError('an empty phoneme sequence cannot be aligned')
         if len(sequence) > MAX_PHONEMES:
             raise ValueError(f'alignment takes at most {MAX_PHONEMES} phonemes, got {len(sequence)}')
-        if len(sequence) > frames:
+        if fit and len(sequence) > frames:
             raise ValueError(f'{len(sequence)} phonemes do not fit {frames} frames: every phoneme takes a frame')
     return sequences
 
 
-def forced(ppg, phonemes, lengths=None, phoneme_lengths=None, gop=True):
+def _flags(optional, sequences, batched, lengths):
+    """The `optional` of a call as a list of bool lists, one per item, each a legal companion of its transcript."""
+    if torch.is_tensor(optional):
+        if optional.is_floating_point() or optional.is_complex() or optional.dim() != (2 if batched else 1):
+            raise ValueError(f'optional must be a bool or integer tensor with the shape of the phonemes, got '
+                             f'{tuple(optional.shape)} {optional.dtype}')
+        rows = optional.detach().cpu().tolist()
+        rows = rows if batched else [rows]
+        if len(rows) != len(sequences):
+            raise ValueError(f'optional has {len(rows)} rows for a batch of {len(sequences)}')
+        for row, sequence in zip(rows, sequences):
+            if len(row) < len(sequence):
+                raise ValueError(f'optional has {len(row)} flags for {len(sequence)} phonemes')
+        # (a padded table's entries past an item's own phonemes are padding, as in the phoneme table)
+        rows = [row[:len(sequence)] if batched else row for row, sequence in zip(rows, sequences)]
+    else:
+        if not isinstance(optional, (list, tuple)):
+            raise ValueError(f'optional must be a list of bools per sequence, got {type(optional).__name__}')
+        rows = list(optional) if batched else [optional]
+        if len(rows) != len(sequences):
+            raise ValueError(f'optional has {len(rows)} entries for a batch of {len(sequences)}')
+        for row in rows:
+            if torch.is_tensor(row):
+                if row.dim() != 1 or row.is_floating_point() or row.is_complex():
+                    raise ValueError('the optional flags of a sequence must be one-dimensional bools or integers')
+            elif not isinstance(row, (list, tuple)):
+                raise ValueError(f'the optional flags of a sequence must be a list of bools, got {type(row).__name__}')
+        rows = [row.detach().cpu().tolist() if torch.is_tensor(row) else list(row) for row in rows]
+    out = []
+    for row, sequence, frames in zip(rows, sequences, lengths):
+        if len(row) != len(sequence):
+            raise ValueError(f'optional has {len(row)} flags for {len(sequence)} phonemes')
+        for value in row:
+            if not isinstance(value, (bool, int)):
+                raise ValueError(f'an optional flag must be a bool, got {value!r}')
+        row = [bool(value) for value in row]
+        if any(a and b for a, b in zip(row, row[1:])):
+            raise ValueError('two adjacent phonemes are optional: a skip passes over one phoneme only')
+        mandatory = row.count(False)
+        if mandatory < 1:
+            raise ValueError('every phoneme is optional: at least one must be mandatory')
+        if mandatory > frames:
+            raise ValueError(f'{mandatory} mandatory phonemes do not fit {frames} frames: each takes a frame')
+        out.append(row)
+    return out
+
+
+def forced(ppg, phonemes, lengths=None, phoneme_lengths=None, gop=True, optional=None):
     """Align `ppg` to the phonemes the speaker was meant to say: Alignment(phonemes, starts, total, score, gop).
 
     `ppg` is (40, T) with `phonemes` a list of names from `ppgs_amd.PHONEMES` or of indices, or an integer tensor; or a
@@ -147,24 +211,97 @@ def forced(ppg, phonemes, lengths=None, phoneme_lengths=None, gop=True):
     list of B such sequences, or a padded (B, Nmax) integer tensor with `phoneme_lengths`.  One utterance returns
     device tensors: phonemes (N,) int32, starts (N + 1,) int32, total 0-d, score and gop (N,) fp32.  A batch returns
     lists of B such tensors for the ragged fields and total (B,).  gop=False skips that sum and returns None for it.
-    A batch equals its single calls bit for bit."""
+    A batch equals its single calls bit for bit.
+
+    `optional` marks phonemes the speaker may leave out (see the module's text): a list of bools per sequence, for a
+    batch a list of such lists or a (B, Nmax) bool or integer tensor.  A phoneme that was left out has
+    starts[n] == starts[n + 1] and NaN for its score and gop.  A sequence may then be longer than its frames, as long
+    as its mandatory phonemes fit.  With None the call is the plain alignment."""
     batched, batch, frames = _ppg(ppg)
     if not batched and lengths is not None:
         raise ValueError('lengths go with a batch: slice a single PPG instead')
     lengths = _lengths(lengths, batch, frames)
-    sequences = _sequences(phonemes, phoneme_lengths, batched, batch, lengths)
+    sequences = _sequences(phonemes, phoneme_lengths, batched, batch, lengths, fit=optional is None)
     counts = [len(sequence) for sequence in sequences]
     most = max(counts)
+    flags = None
+    if optional is not None:
+        flags = _flags(optional, sequences, batched, lengths)
+        flags = torch.tensor([row + [False] * (most - len(row)) for row in flags], dtype=torch.int32)
     device = core.device_for(None, ppg)
     table = torch.tensor([sequence + [-1] * (most - len(sequence)) for sequence in sequences], dtype=torch.int32)
     table = table.to(device)
     x = ppg.to(device)
-    total, starts, score, below = engine.align_items(x if batched else x[None], lengths, table, counts, gop)
+    total, starts, score, below = engine.align_items(x if batched else x[None], lengths, table, counts, gop,
+                                                     optional=None if flags is None else flags.to(device))
     if not batched:
         return Alignment(table[0], starts[0], total[0], score[0], below[0] if gop else None)
     return Alignment(
         [table[b, :n] for b, n in enumerate(counts)], [starts[b, :n + 1] for b, n in enumerate(counts)], total,
         [score[b, :n] for b, n in enumerate(counts)], [below[b, :n] for b, n in enumerate(counts)] if gop else None)
+
+
+def transcript(words, silence=True):
+    """A transcript of words for `forced`: (phonemes, optional, word_of), three lists of one length.
+
+    `words` is a list of words, each a non-empty list of phoneme names (or indices).  With `silence` an optional
+    '<silent>' stands before the first word, between words and after the last: the pauses a speaker may or may not
+    make.  phonemes holds names, optional the flags for `forced(..., optional=)`, and word_of[n] the index in `words`
+    of the word phoneme n belongs to, -1 for the inserted silences.  Host only."""
+    if isinstance(words, (str, bytes)) or not isinstance(words, (list, tuple)) or len(words) < 1:
+        raise ValueError('a transcript takes a non-empty list of words, each a list of phonemes')
+    phonemes, optional, word_of = [], [], []
+
+    def pause():
+        phonemes.append('<silent>')
+        optional.append(True)
+        word_of.append(-1)
+    for index, word in enumerate(words):
+        names = [PHONEMES[value] for value in _sequence(word)]
+        if not names:
+            raise ValueError(f'word {index} has no phonemes')
+        if silence:
+            pause()
+        phonemes.extend(names)
+        optional.extend([False] * len(names))
+        word_of.extend([index] * len(names))
+    if silence:
+        pause()
+    return phonemes, optional, word_of
+
+
+def word_segments(alignment, word_of, sample_rate=config.SAMPLE_RATE, hopsize=config.HOPSIZE):
+    """The words of an alignment of one utterance as a host list of (word index, start seconds, end seconds, gop), one
+    per word of `word_of` (as `transcript` returns it; phonemes with -1 belong to no word).  A word lasts from the
+    start of its first phoneme to the end of its last; its gop is the mean of its present phonemes' gop (those that
+    were given frames), NaN if none is present, None if the alignment has no gop.  A batch (lists in the alignment)
+    takes a list of `word_of` lists and gives a list of such lists.  Host only."""
+    phonemes, starts, gop = alignment.phonemes, alignment.starts, getattr(alignment, 'gop', None)
+    if isinstance(phonemes, (list, tuple)):
+        if not isinstance(word_of, (list, tuple)) or len(word_of) != len(phonemes):
+            raise ValueError(f'a batch of {len(phonemes)} alignments takes {len(phonemes)} word_of lists')
+        return [word_segments(Alignment(phonemes[b], starts[b], None, None, None if gop is None else gop[b]),
+                              word_of[b], sample_rate, hopsize) for b in range(len(phonemes))]
+    frames = starts.tolist()
+    word_of = [int(value) for value in word_of]
+    if len(frames) != len(word_of) + 1 or len(word_of) != phonemes.shape[0]:
+        raise ValueError(f'{phonemes.shape[0]} phonemes take as many word_of entries and one more start, got '
+                         f'{len(word_of)} and {len(frames)}')
+    values = None if gop is None else gop.tolist()
+    out = []
+    for index in sorted(set(word_of) - {-1}):
+        if index < 0:
+            raise ValueError(f'word_of: {index} is neither a word index nor -1')
+        members = [n for n, value in enumerate(word_of) if value == index]
+        if members != list(range(members[0], members[-1] + 1)):
+            raise ValueError(f'the phonemes of word {index} are not adjacent')
+        mean = None
+        if values is not None:
+            present = [values[n] for n in members if frames[n] < frames[n + 1]]
+            mean = sum(present) / len(present) if present else math.nan
+        out.append((index, frames[members[0]] * hopsize / sample_rate, frames[members[-1] + 1] * hopsize / sample_rate,
+                    mean))
+    return out
 
 
 def decode(ppg, lengths=None):

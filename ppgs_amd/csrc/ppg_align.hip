@@ -7,7 +7,7 @@
 //   the path advances (takes n-1) only if D[t-1, n-1] > D[t-1, n]; a tie stays.  Comparisons only.
 //   total = D[T-1, N-1]; the trace-back starts at (T-1, N-1).
 //
-// Five kernels, all on the caller's stream, no allocation, no synchronisation:
+// Five kernels (and three for optional phonemes, below), all on the caller's stream, no allocation, no synchronisation:
 //   align_prepare    one thread per frame: the 40 clamped log-posteriors and their maximum, frame-major (176 B per
 //                    frame).  ONE piece of code for every consumer, so a frame always gives the same bits.
 //   align_programme  one wave per utterance.  Lane l keeps a strip of S consecutive states (their phoneme and
@@ -21,6 +21,17 @@
 //   align_score      one thread per (utterance, phoneme): its segment summed in frame order.
 //   decode_runs      one wave per utterance: per-frame argmax (lowest index on ties), run boundaries compacted with
 //                    ballot and a popcount prefix.
+//
+// Optional phonemes (ppg_align_optional): opt[n] != 0 lets the path jump over phoneme n.
+//   D[t, n] = e[t, n] + best of  stay D[t-1, n],  advance D[t-1, n-1],  skip D[t-1, n-2] if opt[n-1]
+//   strict comparisons in that order: stay beats advance beats skip on ties.  State -1 holds 0 before frame 0.
+//   The end is state N-1, or N-2 if opt[N-1] and D[T-1, N-2] > D[T-1, N-1].
+// align_prepare is shared; three kernels of their own beside the ones above, which stay as they are:
+//   align_programme_optional   the same wave, strips and staging; a second value from below the strip (a second
+//                              cross-lane move), the states' skip permissions as a bit mask in one register, and two
+//                              direction planes (advance, skip) of the 16-bit-per-lane format.
+//   align_traceback_optional   both planes through LDS 64 frames at a time; a skip writes two starts.
+//   align_score_optional       align_score for transcripts that may be longer than the utterance.
 #include "../../include/ppgs_amd.h"
 
 #include <hip/hip_runtime.h>
@@ -48,6 +59,10 @@ struct Layout {
     size_t logp, dirs, bytes;                 // byte offsets into the workspace
 };
 
+struct OptionalLayout {
+    size_t logp, dirs, skips, ends, bytes;    // as Layout, then the skip plane and the end state of every utterance
+};
+
 inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 
 inline Layout layout(int items, int frames) {
@@ -55,6 +70,17 @@ inline Layout layout(int items, int frames) {
     size_t at = 0;
     w.logp = at; at = align256(at + (size_t)items * frames * PREP * sizeof(float));
     w.dirs = at; at = align256(at + (size_t)items * frames * ROW * sizeof(uint16_t));
+    w.bytes = at;
+    return w;
+}
+
+inline OptionalLayout optional_layout(int items, int frames) {
+    OptionalLayout w{};
+    size_t at = 0;
+    w.logp = at; at = align256(at + (size_t)items * frames * PREP * sizeof(float));
+    w.dirs = at; at = align256(at + (size_t)items * frames * ROW * sizeof(uint16_t));
+    w.skips = at; at = align256(at + (size_t)items * frames * ROW * sizeof(uint16_t));
+    w.ends = at; at = align256(at + (size_t)items * sizeof(int));
     w.bytes = at;
     return w;
 }
@@ -309,6 +335,222 @@ __global__ __launch_bounds__(64) void decode_runs(const float* __restrict__ ppg,
     if (lane == 0) { runs[item] = base; out_starts[base] = T; }
 }
 
+// ---- optional phonemes ----
+
+// The programme with optional phonemes of one utterance with S states per lane: `programme` with a third predecessor.
+// Returns the end state; *total is D there.  Everything here is wave-uniform control flow.
+template <int S>
+__device__ __forceinline__ int programme_optional(const float4* __restrict__ src, int T, int N,
+                                                  const int* __restrict__ sym, const int* __restrict__ opt,
+                                                  uint16_t* __restrict__ dirs, uint16_t* __restrict__ skips,
+                                                  float4 (&stage)[2][CHUNK_VEC], int lane, float* total)
+{
+    int s[S]; float d[S];
+    uint32_t may = 0;                                          // bit k: the state below state k of the strip is optional
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        const int n = lane * S + k;
+        s[k] = n < N ? sym[n] : 0;                             // states at or above N run along on phoneme 0, unread
+        may |= (uint32_t)(n >= 1 && n < N && opt[n - 1] != 0) << k;
+        d[k] = -INFINITY;
+    }
+    float4 next[FETCH];
+    fetch(src, 0, T, lane, next);
+    stash(stage[0], lane, next);
+    __syncthreads();
+    int buf = 0;
+    for (int t0 = 0; t0 < T; t0 += CHUNK, buf ^= 1) {
+        fetch(src, t0 + CHUNK, T, lane, next);                 // in flight while this chunk is consumed
+        const float* e = reinterpret_cast<const float*>(stage[buf]);
+        const int count = min(CHUNK, T - t0);
+        float cur[S];                                          // frame t's emissions, read one frame ahead of their use
+#pragma unroll
+        for (int k = 0; k < S; ++k) cur[k] = e[s[k]];
+        for (int u = 0; u < count; ++u) {
+            const int t = t0 + u;
+            const float* ahead = e + min(u + 1, CHUNK - 1) * PREP;       // (the last one re-reads a row: unused)
+            float coming[S];
+#pragma unroll
+            for (int k = 0; k < S; ++k) coming[k] = ahead[s[k]];
+            // the two states below the strip.  The virtual origin, state -1, holds 0 before frame 0 and -inf after it:
+            // it is `below` of state 0 and, where phoneme 0 is optional, `under` of state 1.
+            const float below = lane_up(d[S - 1], t == 0 ? 0.f : -INFINITY);
+            const float under = S == 1 ? lane_up(below, -INFINITY) : lane_up(d[S > 1 ? S - 2 : 0], -INFINITY);
+            uint32_t bits = 0, jumps = 0;
+#pragma unroll
+            for (int k = S - 1; k >= 0; --k) {                 // downwards: d[k - 1] and d[k - 2] are still frame t-1's
+                const float stay = d[k], from = k ? d[k - 1] : below;
+                const float over = k >= 2 ? d[k >= 2 ? k - 2 : 0] : k == 1 ? below : under;
+                const bool advance = from > stay;
+                const float best = advance ? from : stay;
+                const bool skip = ((may >> k) & 1) && over > best;
+                d[k] = cur[k] + (skip ? over : best);          // -inf + finite = -inf: never NaN
+                bits |= (uint32_t)advance << k;                // (a set skip bit overrides it in the trace-back)
+                jumps |= (uint32_t)skip << k;
+            }
+            dirs[(size_t)t * ROW + lane] = (uint16_t)bits;
+            skips[(size_t)t * ROW + lane] = (uint16_t)jumps;
+#pragma unroll
+            for (int k = 0; k < S; ++k) cur[k] = coming[k];
+        }
+        stash(stage[buf ^ 1], lane, next);
+        __syncthreads();
+    }
+    const int k = (N - 1) % S, j = (N + S - 2) % S;            // the last state's place in its strip; the one below it
+    float last = d[0], before = d[0];
+#pragma unroll
+    for (int q = 1; q < S; ++q) {
+        last = k == q ? d[q] : last;
+        before = j == q ? d[q] : before;
+    }
+    last = __shfl(last, (N - 1) / S);
+    before = __shfl(before, max(N - 2, 0) / S);
+    const bool shorter = N >= 2 && opt[N - 1] != 0 && before > last;       // (uniform) the last phoneme is left out
+    *total = shorter ? before : last;
+    return shorter ? N - 2 : N - 1;
+}
+
+// grid (items), 64 threads.  An utterance that cannot be aligned gets total = NaN and nothing else.
+__global__ __launch_bounds__(64) void align_programme_optional(const float* __restrict__ logp, int frames,
+                                                                const int* __restrict__ lengths,
+                                                                const int* __restrict__ phonemes,
+                                                                const int* __restrict__ optional, int max_phonemes,
+                                                                const int* __restrict__ phoneme_lengths,
+                                                                uint16_t* __restrict__ dirs,
+                                                                uint16_t* __restrict__ skips, int* __restrict__ ends,
+                                                                float* __restrict__ total)
+{
+    __shared__ float4 stage[2][CHUNK_VEC];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item], N = phoneme_lengths[item];
+    const int* sym = phonemes + (size_t)item * max_phonemes;
+    const int* opt = optional + (size_t)item * max_phonemes;
+    bool fine = T >= 1 && T <= frames && N >= 1 && N <= max_phonemes;
+    if (fine) {
+        bool bad = false;
+        int mandatory = 0;
+        for (int base = 0; base < N; base += 64) {             // (uniform)
+            const int n = base + lane;
+            bool needed = false;
+            if (n < N) {
+                needed = opt[n] == 0;
+                bad |= (unsigned)sym[n] >= (unsigned)NP;
+                bad |= !needed && n + 1 < N && opt[n + 1] != 0;            // two optional phonemes in a row
+            }
+            mandatory += __popcll(__ballot(needed));
+        }
+        fine = !__any(bad) && mandatory >= 1 && mandatory <= T;
+    }
+    if (!fine) {                                               // (uniform)
+        if (lane == 0) total[item] = NAN;
+        return;
+    }
+    const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
+    uint16_t* out = dirs + (size_t)item * frames * ROW;
+    uint16_t* jumps = skips + (size_t)item * frames * ROW;
+    const int shift = strip_shift(N);
+    float sum;
+    int end;
+    if (shift == 0) end = programme_optional<1>(src, T, N, sym, opt, out, jumps, stage, lane, &sum);
+    else if (shift == 2) end = programme_optional<4>(src, T, N, sym, opt, out, jumps, stage, lane, &sum);
+    else end = programme_optional<16>(src, T, N, sym, opt, out, jumps, stage, lane, &sum);
+    if (lane == 0) { total[item] = sum; ends[item] = end; }
+}
+
+// grid (items), 64 threads.  An utterance whose total is NaN was refused by the programme, which checked its lengths:
+// starts stay untouched.  Every other utterance has its end state in `ends`.
+__global__ __launch_bounds__(64) void align_traceback_optional(const uint16_t* __restrict__ dirs,
+                                                                const uint16_t* __restrict__ skips, int frames,
+                                                                const int* __restrict__ lengths, int max_phonemes,
+                                                                const int* __restrict__ phoneme_lengths,
+                                                                const float* __restrict__ total,
+                                                                const int* __restrict__ ends, int* __restrict__ starts)
+{
+    __shared__ uint4 rows[2][WALK * ROW_VEC];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    if (total[item] != total[item]) return;
+    const int T = lengths[item], N = phoneme_lengths[item];
+    const int shift = strip_shift(N), mask = (1 << shift) - 1;
+    const uint4* src = reinterpret_cast<const uint4*>(dirs + (size_t)item * frames * ROW);
+    const uint4* src_skips = reinterpret_cast<const uint4*>(skips + (size_t)item * frames * ROW);
+    int* out = starts + (size_t)item * (max_phonemes + 1);
+    uint4 next[2][ROW_VEC];
+    auto load = [&](int c) {                                   // rows of frames c * WALK ..., those below T only
+        const int pieces = min(WALK, T - c * WALK) * ROW_VEC;
+#pragma unroll
+        for (int u = 0; u < ROW_VEC; ++u) {
+            const int idx = u * 64 + lane;
+            const bool in = idx < pieces;
+            next[0][u] = in ? src[(size_t)c * WALK * ROW_VEC + idx] : make_uint4(0, 0, 0, 0);
+            next[1][u] = in ? src_skips[(size_t)c * WALK * ROW_VEC + idx] : make_uint4(0, 0, 0, 0);
+        }
+    };
+    const int end = min(max(ends[item], 0), N - 1);
+    int n = end;
+    int c = (T - 1) / WALK;
+    load(c);
+    for (; c >= 0; --c) {
+        __syncthreads();                                       // the walk over the previous refill is over
+#pragma unroll
+        for (int u = 0; u < ROW_VEC; ++u) {
+            rows[0][u * 64 + lane] = next[0][u];
+            rows[1][u * 64 + lane] = next[1][u];
+        }
+        __syncthreads();
+        if (c > 0) load(c - 1);
+        const uint16_t* row = reinterpret_cast<const uint16_t*>(rows[0]);
+        const uint16_t* row_skips = reinterpret_cast<const uint16_t*>(rows[1]);
+        const int low = max(c * WALK, 1);
+        for (int t = min(T - 1, c * WALK + WALK - 1); t >= low; --t) {
+            const int at = (t & (WALK - 1)) * ROW + (n >> shift), bit = n & mask;  // the same address in every lane
+            const uint32_t word = row[at], jump = row_skips[at];
+            if (n > 1 && ((jump >> bit) & 1)) {                // over the optional phoneme n - 1: it gets no frame
+                if (lane == 0) { out[n] = t; out[n - 1] = t; }
+                n -= 2;
+            } else if (n > 0 && ((word >> bit) & 1)) {
+                if (lane == 0) out[n] = t;
+                --n;
+            }
+        }
+    }
+    if (lane == 0) {
+        if (n == 1) out[1] = 0;                                // the path began in state 1: phoneme 0 was left out
+        out[0] = 0;
+        if (end == N - 2) out[N - 1] = T;                      // ... ended in state N - 2: phoneme N - 1 was left out
+        out[N] = T;
+    }
+}
+
+// grid (ceil(max_phonemes / 64), items), 64 threads: thread = phoneme.  align_score, statement for statement, without
+// its refusal of N > T: the programme has checked the lengths of every utterance whose total is not NaN.  A phoneme
+// that was left out has an empty segment: 0 / 0 = NaN.
+__global__ __launch_bounds__(64) void align_score_optional(const float* __restrict__ logp, int frames,
+                                                            const int* __restrict__ lengths,
+                                                            const int* __restrict__ phonemes, int max_phonemes,
+                                                            const int* __restrict__ phoneme_lengths,
+                                                            const float* __restrict__ total,
+                                                            const int* __restrict__ starts,
+                                                            float* __restrict__ score, float* __restrict__ gop)
+{
+    const int item = blockIdx.y, n = blockIdx.x * 64 + threadIdx.x;
+    if (total[item] != total[item]) return;
+    const int T = lengths[item], N = phoneme_lengths[item];
+    if (n >= N) return;
+    const int* bounds = starts + (size_t)item * (max_phonemes + 1) + n;
+    const int first = max(bounds[0], 0), end = min(bounds[1], T);
+    const float* row = logp + (size_t)item * frames * PREP + phonemes[(size_t)item * max_phonemes + n];
+    const float* top = logp + (size_t)item * frames * PREP + NP;
+    float sum = 0.f, below = 0.f;
+    for (int t = first; t < end; ++t) {
+        const float e = row[(size_t)t * PREP];
+        sum += e;
+        if (gop) below += e - top[(size_t)t * PREP];           // exactly 0 where the target is the frame's maximum
+    }
+    const float count = (float)(end - first);
+    score[(size_t)item * max_phonemes + n] = sum / count;
+    if (gop) gop[(size_t)item * max_phonemes + n] = below / count;
+}
+
 int check_common(const char* what, const void* ppg, int frames, int items, const void* lengths) {
     if (!ppg || !lengths || items <= 0 || frames <= 0) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
     if (frames > PPG_ALIGN_MAX_FRAMES)
@@ -357,6 +599,48 @@ int ppg_align(int device, const float* ppg, int frames, int items, const int32_t
                        phonemes, max_phonemes, phoneme_lengths, total, starts, score, gop);
     const hipError_t he = hipGetLastError();
     return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "align: %s", hipGetErrorString(he));
+}
+
+size_t ppg_align_optional_workspace_bytes(int items, int frames, int max_phonemes) {
+    if (items <= 0 || items > PPG_ALIGN_MAX_ITEMS || frames <= 0 || frames > PPG_ALIGN_MAX_FRAMES ||
+        max_phonemes <= 0 || max_phonemes > PPG_ALIGN_MAX_PHONEMES)
+        return 0;
+    return optional_layout(items, frames).bytes;
+}
+
+int ppg_align_optional(int device, const float* ppg, int frames, int items, const int32_t* lengths,
+                       const int32_t* phonemes, const int32_t* optional, int max_phonemes,
+                       const int32_t* phoneme_lengths, float* total, int32_t* starts, float* score, float* gop,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = check_common("align_optional", ppg, frames, items, lengths)) return rc;
+    if (!phonemes || !optional || !phoneme_lengths || !total || !starts || !score || !workspace || max_phonemes <= 0)
+        return ppg::fail_message(PPG_EINVAL, "align_optional: bad argument");
+    if (max_phonemes > PPG_ALIGN_MAX_PHONEMES)
+        return ppg::fail_message(PPG_EINVAL, "align_optional: %d phonemes, at most %d", max_phonemes,
+                                 PPG_ALIGN_MAX_PHONEMES);
+    const OptionalLayout w = optional_layout(items, frames);
+    if (workspace_bytes < w.bytes)
+        return ppg::fail_message(PPG_EINVAL, "align_optional: workspace of %zu bytes, %zu needed", workspace_bytes,
+                                 w.bytes);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16)
+        return ppg::fail_message(PPG_EINVAL, "align_optional: workspace must be 16-byte aligned");
+    if (hipSetDevice(device) != hipSuccess)
+        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    float* logp = reinterpret_cast<float*>(ws + w.logp);
+    uint16_t* dirs = reinterpret_cast<uint16_t*>(ws + w.dirs);
+    uint16_t* skips = reinterpret_cast<uint16_t*>(ws + w.skips);
+    int* ends = reinterpret_cast<int*>(ws + w.ends);
+    hipLaunchKernelGGL(align_prepare, dim3((frames + 63) / 64, items), dim3(64), 0, s, ppg, frames, lengths, logp);
+    hipLaunchKernelGGL(align_programme_optional, dim3(items), dim3(64), 0, s, logp, frames, lengths, phonemes, optional,
+                       max_phonemes, phoneme_lengths, dirs, skips, ends, total);
+    hipLaunchKernelGGL(align_traceback_optional, dim3(items), dim3(64), 0, s, dirs, skips, frames, lengths,
+                       max_phonemes, phoneme_lengths, total, ends, starts);
+    hipLaunchKernelGGL(align_score_optional, dim3((max_phonemes + 63) / 64, items), dim3(64), 0, s, logp, frames,
+                       lengths, phonemes, max_phonemes, phoneme_lengths, total, starts, score, gop);
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "align_optional: %s", hipGetErrorString(he));
 }
 
 int ppg_decode(int device, const float* ppg, int frames, int items, const int32_t* lengths, int32_t* phonemes,

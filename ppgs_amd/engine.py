@@ -153,6 +153,11 @@ SYMBOLS = {
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_size_t, ctypes.c_void_p]),
+    'ppg_align_optional_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_align_optional': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'ppg_decode': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -720,11 +725,13 @@ def _items(ppg, lengths, what):
     return x, lengths
 
 
-def align_items(ppg, lengths, phonemes, phoneme_lengths, want_gop=True):
+def align_items(ppg, lengths, phonemes, phoneme_lengths, want_gop=True, optional=None):
     """Forced alignment of item b = ppg[b, :, :lengths[b]] to phonemes[b, :phoneme_lengths[b]] (ppg_align):
     (items, 40, frames) on a GPU, phonemes a padded (items, max_phonemes) integer tensor, both lengths as host
     integers -> total (items,) fp32, starts (items, max_phonemes + 1) int32, score and gop (items, max_phonemes) fp32
-    (gop None without want_gop).  Entries past an item's own N (N + 1 for starts) are zero."""
+    (gop None without want_gop).  Entries past an item's own N (N + 1 for starts) are zero.  With `optional`, a table
+    of the shape of `phonemes` whose non-zero entries mark phonemes that may be left out, ppg_align_optional runs
+    instead: a phoneme that was left out has starts[n] == starts[n + 1] and NaN for its score and gop."""
     x, lengths = _items(ppg, lengths, 'align')
     items, frames = x.shape[0], x.shape[2]
     device = x.device
@@ -733,6 +740,10 @@ def align_items(ppg, lengths, phonemes, phoneme_lengths, want_gop=True):
             f'phonemes must be ({items}, 1 to {ALIGN_MAX_PHONEMES}) for {items} items, got {tuple(phonemes.shape)}')
     table = phonemes.to(device=device, dtype=torch.int32).contiguous()
     most = table.shape[1]
+    if optional is not None:
+        if tuple(optional.shape) != tuple(table.shape):
+            raise ValueError(f'optional must have the shape of phonemes {tuple(table.shape)}, got {tuple(optional.shape)}')
+        optional = optional.to(device=device, dtype=torch.int32).contiguous()
     phoneme_lengths = [int(v) for v in phoneme_lengths]
     if len(phoneme_lengths) != items:
         raise ValueError(f'{len(phoneme_lengths)} phoneme lengths for {items} items')
@@ -742,16 +753,25 @@ def align_items(ppg, lengths, phonemes, phoneme_lengths, want_gop=True):
     score = torch.zeros((items, most), dtype=torch.float32, device=device)
     gop = torch.zeros((items, most), dtype=torch.float32, device=device) if want_gop else None
     lib = library()
-    group = max(1, min(items, ALIGN_MAX_ITEMS, ALIGN_WORKSPACE_BYTES // lib.ppg_align_workspace_bytes(1, frames, most)))
-    size = lib.ppg_align_workspace_bytes(group, frames, most)
+    bytes_for = lib.ppg_align_workspace_bytes if optional is None else lib.ppg_align_optional_workspace_bytes
+    group = max(1, min(items, ALIGN_MAX_ITEMS, ALIGN_WORKSPACE_BYTES // bytes_for(1, frames, most)))
+    size = bytes_for(group, frames, most)
     workspace = torch.empty((size,), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream().cuda_stream
         for at in range(0, items, group):
-            _check(lib.ppg_align(
-                device.index, x[at:].data_ptr(), frames, min(group, items - at), both[0, at:].data_ptr(),
-                table[at:].data_ptr(), most, both[1, at:].data_ptr(), total[at:].data_ptr(), starts[at:].data_ptr(),
-                score[at:].data_ptr(), gop[at:].data_ptr() if want_gop else None, workspace.data_ptr(), size, stream))
+            if optional is None:
+                _check(lib.ppg_align(
+                    device.index, x[at:].data_ptr(), frames, min(group, items - at), both[0, at:].data_ptr(),
+                    table[at:].data_ptr(), most, both[1, at:].data_ptr(), total[at:].data_ptr(),
+                    starts[at:].data_ptr(), score[at:].data_ptr(), gop[at:].data_ptr() if want_gop else None,
+                    workspace.data_ptr(), size, stream))
+            else:
+                _check(lib.ppg_align_optional(
+                    device.index, x[at:].data_ptr(), frames, min(group, items - at), both[0, at:].data_ptr(),
+                    table[at:].data_ptr(), optional[at:].data_ptr(), most, both[1, at:].data_ptr(),
+                    total[at:].data_ptr(), starts[at:].data_ptr(), score[at:].data_ptr(),
+                    gop[at:].data_ptr() if want_gop else None, workspace.data_ptr(), size, stream))
     return total, starts, score, gop
 
 
