@@ -552,6 +552,66 @@ int ppg_align_optional(int device, const float* ppg, int frames, int items, cons
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Phrase search: where in a recording is a phoneme sequence said, and how well (keyword spotting on posteriorgrams).
+ * ppg_align pins its transcript to frame 0 and frame T-1; here the match may start and end at any frame.  Not in the
+ * reference.
+ *
+ * One pair is a recording P (40, T) and a query s[0 .. N-1], 1 <= N <= PPG_SEARCH_MAX_PHONEMES.
+ *   logp[t][q] = logf(min(max(P[q, t], 1e-8), 1 - 1e-8)) and m[t] = max_q logp[t][q]: the prepared frame of ppg_align,
+ *   bit for bit (the same kernel).
+ *   r[t, n] = logp[t][s[n]] - m[t] in fp32: the log-likelihood ratio against the free phone loop, <= 0, and exactly 0
+ *   where the target is the frame's most likely phoneme.
+ *   Before frame 0 every state holds -inf.
+ *   D[t, 0] = r[t, 0] + (0 > D[t-1, 0] ? 0 : D[t-1, 0]): a fresh start, b[t, 0] = t, only if strictly better; otherwise
+ *            the state stays and b[t, 0] = b[t-1, 0].
+ *   D[t, n > 0] = r[t, n] + max(D[t-1, n], D[t-1, n-1]); the path advances only if D[t-1, n-1] > D[t-1, n], and b[t, n]
+ *            is the b of the predecessor taken.  Comparisons only; fp32; added in order of t.  -inf + finite = -inf and
+ *            -inf > -inf is false: no NaN and no advance from unreachable states.
+ *   The curve, per end frame t: curve_total[t] = D[t, N-1], curve_begin[t] = b[t, N-1]; -inf and -1 for t < N-1.  The
+ *   match ending at t covers frames curve_begin[t] .. t; mean[t] = curve_total[t] / float(t - curve_begin[t] + 1), one
+ *   fp32 division.  Among equal optima for an end frame the last phoneme starts earliest, then the one before it, ...,
+ *   then the earliest begin.
+ *   Hits are chosen in at most `top` rounds.  The candidates of a round are the end frames N-1 <= t < T whose span
+ *   intersects no hit already taken; the largest mean wins, ties go to the LARGEST t (a perfect match runs to the end
+ *   of its last phoneme); the rounds stop when there is no candidate or the best mean < threshold.  A hit is begin,
+ *   end = t + 1 (exclusive), total and mean; hits are pairwise disjoint and listed in the order taken.
+ *
+ * ppg_search: every query is searched in every recording.
+ *   ppg             : device fp32 (items, 40, frames), padded; frames at or past an item's length are never read
+ *   lengths         : device int32[items], each in [1, frames]
+ *   phonemes        : device int32 (queries, max_phonemes), indices 0 .. 39, padded; entries at or past a query's
+ *                     phoneme_lengths are never read
+ *   phoneme_lengths : device int32[queries], each in [1, max_phonemes]
+ *   top, threshold  : 1 <= top <= PPG_SEARCH_MAX_HITS; threshold may be -inf (every round takes a hit), never NaN
+ *   begin, end      : device int32 (items, queries, top)
+ *   total, mean     : device fp32 (items, queries, top); entries at or past count are begin = end = -1, total = mean = NaN
+ *   count           : device int32 (items, queries): the number of hits.  A query longer than its recording (N > T) has
+ *                     count = 0 and a curve of -inf / -1.  A pair that cannot be searched (N < 1, N > max_phonemes, T
+ *                     outside [1, frames], a phoneme index outside 0 .. 39) gets count = -1 and nothing else: its other
+ *                     outputs stay untouched and nothing is accessed out of range.
+ *   curve_total     : device fp32 (items, queries, frames) or NULL; entries t < lengths[item] are written
+ *   curve_begin     : device int32 (items, queries, frames) or NULL, both or neither
+ *   workspace       : device memory, 16-byte aligned, at least ppg_search_workspace_bytes(items, frames, queries)
+ *                     bytes: three blocks, each 256-byte aligned: the prepared frames once per recording (176 B per
+ *                     frame), then the curve of every pair, totals and begins (4 B per frame each)
+ * Kernel launches on `stream` only: no allocation, synchronisation or copy.  Every byte read was written earlier in
+ * the same call.  Every result is a function of its own pair alone: a batch equals its singles bit for bit.
+ * PPG_EINVAL, and nothing launched, for: a NaN threshold, top outside 1 .. PPG_SEARCH_MAX_HITS, a limit exceeded, one
+ * curve pointer without the other, an unaligned or short workspace, a NULL input or output.
+ * ppg_search_workspace_bytes is host-only and returns 0 for impossible arguments.
+ */
+#define PPG_SEARCH_MAX_FRAMES 262144
+#define PPG_SEARCH_MAX_PHONEMES 256
+#define PPG_SEARCH_MAX_HITS 64
+#define PPG_SEARCH_MAX_ITEMS 65535
+#define PPG_SEARCH_MAX_QUERIES 65535
+size_t ppg_search_workspace_bytes(int items, int frames, int queries);
+int ppg_search(int device, const float* ppg, int frames, int items, const int32_t* lengths, const int32_t* phonemes,
+               int max_phonemes, int queries, const int32_t* phoneme_lengths, int top, float threshold,
+               int32_t* begin, int32_t* end, float* total, float* mean, int32_t* count, float* curve_total,
+               int32_t* curve_begin, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Frame metrics accumulated on the device: what the reference's `python -m ppgs.evaluate` computes per batch with
  * five metric objects (ppgs/evaluate/metrics.py: Accuracy, CategoricalAccuracy, JensenShannon, TopKAccuracy, Loss,
  * DistanceMatrix), here ONE kernel launch per batch into one device block, no host synchronisation, read once at

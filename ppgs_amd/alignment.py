@@ -40,6 +40,26 @@ With every flag False the results are those of the plain alignment bit for bit.
     phonemes, optional, word_of = ppgs_amd.alignment.transcript([['hh', 'ah'], ['l', 'ow']])   # <silent> around words
     alignment = ppgs_amd.alignment.forced(ppg, phonemes, optional=optional)
     for word, start, end, gop in ppgs_amd.alignment.word_segments(alignment, word_of): ...
+
+Phrase search (`search`, ppg_search): where in a recording is a phoneme sequence said, and how well?  `forced` pins
+its transcript to frame 0 and frame T-1 and stops at 4096 frames; `search` lets the match start and end anywhere in up
+to 262144 frames.  For a recording P (40, T) and a query s of 1 <= N <= 256 phonemes:
+
+    r[t, n] = logp[t][s[n]] - max_q logp[t][q]     the GOP term of `forced`: <= 0, exactly 0 at the frame's maximum
+    before frame 0 every state holds -inf
+    D[t, 0] = r[t, 0] + (0 > D[t-1, 0] ? 0 : D[t-1, 0])      a fresh start, b[t, 0] = t, only if strictly better
+    D[t, n] = r[t, n] + max(D[t-1, n], D[t-1, n-1])           advance only if D[t-1, n-1] > D[t-1, n]; b follows the path
+
+The curve is, per end frame t, curve_total[t] = D[t, N-1] and curve_begin[t] = b[t, N-1] (-inf and -1 for t < N-1): the
+best match ending at t covers frames curve_begin[t] .. t, and mean[t] = curve_total[t] / (t - curve_begin[t] + 1).  Hits
+are taken in at most `top` rounds: of the end frames whose span meets no hit already taken, the largest mean, ties to
+the largest t; the rounds stop when nothing is left or the best mean < threshold.  A hit is (begin, end = t + 1, total,
+mean); hits are disjoint and listed in the order taken.  Entries past `count` are -1, -1, NaN, NaN.
+
+    hits = ppgs_amd.alignment.search(ppg, ['hh', 'ah', 'l', 'ow'], top=5, threshold=-1.)
+    for start, end, total, mean in ppgs_amd.alignment.hit_segments(hits): ...
+    b, e = int(hits.begin[0]), int(hits.end[0])
+    inside = ppgs_amd.alignment.forced(ppg[:, b:e], ['hh', 'ah', 'l', 'ow'])     # the phoneme boundaries inside a hit
 """
 import collections
 import math
@@ -51,12 +71,16 @@ from .phonemes import PHONEMES, PHONEME_TO_INDEX_MAPPING
 
 MAX_FRAMES = engine.ALIGN_MAX_FRAMES
 MAX_PHONEMES = engine.ALIGN_MAX_PHONEMES
+SEARCH_MAX_FRAMES = engine.SEARCH_MAX_FRAMES
+SEARCH_MAX_PHONEMES = engine.SEARCH_MAX_PHONEMES
+SEARCH_MAX_HITS = engine.SEARCH_MAX_HITS
 
 Alignment = collections.namedtuple('Alignment', ['phonemes', 'starts', 'total', 'score', 'gop'])
 Decoding = collections.namedtuple('Decoding', ['phonemes', 'starts'])
+Hits = collections.namedtuple('Hits', ['phonemes', 'begin', 'end', 'total', 'mean', 'count', 'curve'])
 
 
-def _ppg(ppg):
+def _ppg(ppg, most=MAX_FRAMES, what='alignment'):
     """Shape checks of a PPG or a batch of them: (batched, batch, frames)."""
     if not torch.is_tensor(ppg) or ppg.dim() not in (2, 3):
         raise ValueError(f'PPG must be (40, frames) or (batch, 40, frames), got {tuple(getattr(ppg, "shape", ()))}')
@@ -68,8 +92,8 @@ def _ppg(ppg):
     frames = ppg.shape[-1]
     if frames < 1:
         raise ValueError(f'PPG must have at least one frame, got {tuple(ppg.shape)}')
-    if frames > MAX_FRAMES:
-        raise ValueError(f'alignment takes at most {MAX_FRAMES} frames, got {frames}')
+    if frames > most:
+        raise ValueError(f'{what} takes at most {most} frames, got {frames}')
     return batched, ppg.shape[0] if batched else 1, frames
 
 
@@ -322,6 +346,68 @@ def decode(ppg, lengths=None):
     if not batched:
         return Decoding(phonemes[0, :runs[0]], starts[0, :runs[0] + 1])
     return Decoding([phonemes[b, :r] for b, r in enumerate(runs)], [starts[b, :r + 1] for b, r in enumerate(runs)])
+
+
+def search(ppg, phonemes, lengths=None, top=1, threshold=None, curve=False):
+    """Find where `phonemes` is said in `ppg`: Hits(phonemes, begin, end, total, mean, count, curve).
+
+    `ppg` is (40, T), or a batch (B, 40, T) padded to the longest recording with `lengths` per recording (the padding
+    is never read).  `phonemes` is one sequence of names from `ppgs_amd.PHONEMES` or of indices (a list or an integer
+    tensor), or a list of Q such sequences; every sequence is searched in every recording.  begin, end (int32), total
+    and mean (fp32) are device tensors (B, Q, top), count is (B, Q) int32: the B axis is dropped for a single recording
+    and the Q axis for a single sequence.  Hit h of a pair covers frames begin[h] .. end[h] - 1; hits are disjoint and
+    listed best first; entries at or past count are -1, -1, NaN, NaN.  `threshold` ends the list at the first mean
+    below it (None: `top` hits wherever the recording has room for them).  A sequence longer than its recording has
+    count 0.  With `curve` the last field is (curve_total, curve_begin), each (B, Q, T) with the same drops (-inf and
+    -1 before a match can end and past a recording's own length), else None.  Hits.phonemes holds the queries as int32
+    device tensors.  Nothing here waits for the device."""
+    batched, batch, frames = _ppg(ppg, SEARCH_MAX_FRAMES, 'search')
+    if not batched and lengths is not None:
+        raise ValueError('lengths go with a batch: slice a single PPG instead')
+    lengths = _lengths(lengths, batch, frames)
+    several = isinstance(phonemes, (list, tuple)) and len(phonemes) > 0 and all(
+        torch.is_tensor(item) or isinstance(item, (list, tuple)) for item in phonemes)
+    sequences = [_sequence(item) for item in phonemes] if several else [_sequence(phonemes)]
+    for sequence in sequences:
+        if len(sequence) < 1:
+            raise ValueError('an empty phoneme sequence cannot be searched for')
+        if len(sequence) > SEARCH_MAX_PHONEMES:
+            raise ValueError(f'search takes at most {SEARCH_MAX_PHONEMES} phonemes per query, got {len(sequence)}')
+    if isinstance(top, bool) or not isinstance(top, int) or not 1 <= top <= SEARCH_MAX_HITS:
+        raise ValueError(f'top must be an integer from 1 to {SEARCH_MAX_HITS}, got {top!r}')
+    threshold = -math.inf if threshold is None else float(threshold)
+    if math.isnan(threshold):
+        raise ValueError('the threshold is NaN')
+    counts = [len(sequence) for sequence in sequences]
+    most = max(counts)
+    device = core.device_for(None, ppg)
+    table = torch.tensor([sequence + [-1] * (most - len(sequence)) for sequence in sequences], dtype=torch.int32)
+    table = table.to(device)
+    x = ppg.to(device)
+    begin, end, total, mean, count, curves = engine.search_items(x if batched else x[None], lengths, table, counts, top,
+                                                                 threshold, bool(curve))
+
+    def drop(tensor):
+        tensor = tensor if several else tensor[:, 0]
+        return tensor if batched else tensor[0]
+    names = [table[q, :n] for q, n in enumerate(counts)]
+    return Hits(names if several else names[0], drop(begin), drop(end), drop(total), drop(mean), drop(count),
+                None if curves is None else (drop(curves[0]), drop(curves[1])))
+
+
+def hit_segments(hits, sample_rate=config.SAMPLE_RATE, hopsize=config.HOPSIZE):
+    """The hits of a search as a host list of (start seconds, end seconds, total, mean), the first `count` of them, best
+    first; nested per sequence and per recording as the search was (a list per recording of lists per sequence).  Host
+    only: this is where the results are read."""
+    begin, end, count = hits.begin.tolist(), hits.end.tolist(), hits.count.tolist()
+    total, mean = hits.total.tolist(), hits.mean.tolist()
+
+    def walk(begin, end, total, mean, count):
+        if isinstance(count, list):
+            return [walk(*row) for row in zip(begin, end, total, mean, count)]
+        return [(begin[h] * hopsize / sample_rate, end[h] * hopsize / sample_rate, total[h], mean[h])
+                for h in range(max(count, 0))]
+    return walk(begin, end, total, mean, count)
 
 
 def segments(alignment, sample_rate=config.SAMPLE_RATE, hopsize=config.HOPSIZE):

@@ -1,5 +1,5 @@
 // Forced alignment of a PPG to a phoneme sequence with goodness-of-pronunciation scores, and the free-running
-// run-length decode, on the device.
+// run-length decode, on the device.  Phrase search (ppg_search) stands at the end.
 //
 //   e[t, n] = logf(min(max(P[s[n], t], 1e-8), 1 - 1e-8))                      (the clamp of ppg_distance)
 //   D[0, 0] = e[0, 0];  D[0, n > 0] = -inf
@@ -551,6 +551,215 @@ __global__ __launch_bounds__(64) void align_score_optional(const float* __restri
     if (gop) gop[(size_t)item * max_phonemes + n] = below / count;
 }
 
+// ---- phrase search (ppg_search) ----
+//
+// Where in a recording is a phoneme sequence said, and how well: the programme above with a free start at every frame
+// and a free end.  r[t, n] = logp[t][s[n]] - m[t] (the GOP term: <= 0, exactly 0 at the frame's maximum); before frame
+// 0 every state holds -inf.
+//   D[t, 0] = r[t, 0] + (0 > D[t-1, 0] ? 0 : D[t-1, 0])     a fresh start, b[t, 0] = t, only if strictly better
+//   D[t, n] = r[t, n] + max(D[t-1, n], D[t-1, n-1])          advance only if D[t-1, n-1] > D[t-1, n]
+// b[t, n] is the b of the predecessor taken: the first frame of the match that ends in state n at frame t.  The curve
+// is D[t, N-1] and b[t, N-1] per end frame, -inf and -1 for t < N-1.  Two kernels beside align_prepare, which is shared:
+//   search_programme  grid (queries, items), one wave per pair: the wave, strips (S = 1 or 4 by the query's own N),
+//                     staging and gather of align_programme; the emission subtracts the staged maximum, every state
+//                     carries its begin, a second cross-lane move brings the begin from lane l - 1, and lane 0 sees the
+//                     origin (0, b = t) at every frame.  No direction bits: the lane of state N-1 writes the curve.
+//   search_pick       one wave per pair, lanes stride over end frames: per round the largest mean = total / frames, ties
+//                     to the largest end frame; end frames whose span meets the hit just taken are struck out of the
+//                     workspace's copy of the curve, so a round tests against one hit only.
+
+struct SearchLayout {
+    size_t logp, totals, begins, bytes;       // byte offsets into the workspace
+};
+
+// (65535 x 65535 pairs of 262144 frames are 9.0e15 bytes: the limits keep this inside a size_t)
+inline SearchLayout search_layout(int items, int frames, int queries) {
+    SearchLayout w{};
+    const size_t curve = (size_t)items * queries * frames * sizeof(float);
+    size_t at = 0;
+    w.logp = at; at = align256(at + (size_t)items * frames * PREP * sizeof(float));
+    w.totals = at; at = align256(at + curve);
+    w.begins = at; at = align256(at + curve);
+    w.bytes = at;
+    return w;
+}
+
+// lane_up for integers
+__device__ __forceinline__ int lane_up_int(int v, int first) {
+    return __builtin_amdgcn_update_dpp(first, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+}
+
+// The search programme of one pair with S states per lane: `programme` with begins.  Wave-uniform control flow.
+template <int S>
+__device__ __forceinline__ void search_strips(const float4* __restrict__ src, int T, int N, const int* __restrict__ sym,
+                                              float* __restrict__ totals, int* __restrict__ begins,
+                                              float4 (&stage)[2][CHUNK_VEC], int lane)
+{
+    int s[S], b[S]; float d[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        const int n = lane * S + k;
+        s[k] = n < N ? sym[n] : 0;                             // states at or above N run along on phoneme 0, unread
+        d[k] = -INFINITY;
+        b[k] = -1;
+    }
+    const int last = (N - 1) / S, place = (N - 1) % S;         // the lane of state N-1 and its place in the strip
+    float4 next[FETCH];
+    fetch(src, 0, T, lane, next);
+    stash(stage[0], lane, next);
+    __syncthreads();
+    int buf = 0;
+    for (int t0 = 0; t0 < T; t0 += CHUNK, buf ^= 1) {
+        fetch(src, t0 + CHUNK, T, lane, next);                 // in flight while this chunk is consumed
+        const float* e = reinterpret_cast<const float*>(stage[buf]);
+        const int count = min(CHUNK, T - t0);
+        float cur[S];                                          // frame t's emissions, read one frame ahead of their use
+        {
+            const float top = e[NP];
+#pragma unroll
+            for (int k = 0; k < S; ++k) cur[k] = e[s[k]] - top;
+        }
+        for (int u = 0; u < count; ++u) {
+            const int t = t0 + u;
+            const float* ahead = e + min(u + 1, CHUNK - 1) * PREP;       // (the last one re-reads a row: unused)
+            const float top = ahead[NP];
+            float coming[S];
+#pragma unroll
+            for (int k = 0; k < S; ++k) coming[k] = ahead[s[k]] - top;
+            // the state below the strip; below state 0 the origin: 0, beginning at this frame, at every frame
+            const float below = lane_up(d[S - 1], 0.f);
+            const int origin = lane_up_int(b[S - 1], t);
+#pragma unroll
+            for (int k = S - 1; k >= 0; --k) {                 // downwards: d[k - 1] and b[k - 1] are still frame t-1's
+                const float stay = d[k], from = k ? d[k - 1] : below;
+                const int source = k ? b[k - 1] : origin;
+                const bool advance = from > stay;
+                d[k] = cur[k] + (advance ? from : stay);       // -inf + finite = -inf: never NaN
+                b[k] = advance ? source : b[k];
+            }
+            if (lane == last) {
+                float end = d[0];
+                int first = b[0];
+#pragma unroll
+                for (int q = 1; q < S; ++q) {
+                    end = place == q ? d[q] : end;
+                    first = place == q ? b[q] : first;
+                }
+                totals[t] = end;
+                begins[t] = first;
+            }
+#pragma unroll
+            for (int k = 0; k < S; ++k) cur[k] = coming[k];
+        }
+        stash(stage[buf ^ 1], lane, next);
+        __syncthreads();
+    }
+}
+
+// grid (queries, items), 64 threads.  count = -1 for a pair that cannot be searched, which touches nothing else; 0 for
+// every other, whose curve (frames below T) is then in the workspace.
+__global__ __launch_bounds__(64) void search_programme(const float* __restrict__ logp, int frames,
+                                                        const int* __restrict__ lengths,
+                                                        const int* __restrict__ phonemes, int max_phonemes,
+                                                        const int* __restrict__ phoneme_lengths,
+                                                        float* __restrict__ totals, int* __restrict__ begins,
+                                                        int* __restrict__ count)
+{
+    __shared__ float4 stage[2][CHUNK_VEC];
+    const int query = blockIdx.x, item = blockIdx.y, lane = threadIdx.x;
+    const size_t pair = (size_t)item * gridDim.x + query;
+    const int T = lengths[item], N = phoneme_lengths[query];
+    const int* sym = phonemes + (size_t)query * max_phonemes;
+    bool fine = T >= 1 && T <= frames && N >= 1 && N <= max_phonemes;
+    if (fine) {
+        bool bad = false;
+        for (int n = lane; n < N; n += 64) bad |= (unsigned)sym[n] >= (unsigned)NP;
+        fine = !__any(bad);
+    }
+    if (lane == 0) count[pair] = fine ? 0 : -1;
+    if (!fine) return;                                         // (uniform)
+    const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
+    float* out_totals = totals + pair * frames;
+    int* out_begins = begins + pair * frames;
+    if (N <= 64) search_strips<1>(src, T, N, sym, out_totals, out_begins, stage, lane);
+    else search_strips<4>(src, T, N, sym, out_totals, out_begins, stage, lane);
+}
+
+constexpr int PICK = 4;                       // end frames per lane in flight in the picker
+
+// grid (queries, items), 64 threads.  totals and begins are the workspace's curve: end frames that can no longer be
+// taken get begin = -1 there.  Every lane strikes out and later reads its own end frames only.
+__global__ __launch_bounds__(64) void search_pick(int frames, const int* __restrict__ lengths,
+                                                   const int* __restrict__ phoneme_lengths, int top, float threshold,
+                                                   float* __restrict__ totals, int* __restrict__ begins,
+                                                   int* __restrict__ begin, int* __restrict__ end,
+                                                   float* __restrict__ total, float* __restrict__ mean,
+                                                   int* __restrict__ count, float* __restrict__ curve_total,
+                                                   int* __restrict__ curve_begin)
+{
+    const int query = blockIdx.x, item = blockIdx.y, lane = threadIdx.x;
+    const size_t pair = (size_t)item * gridDim.x + query;
+    if (count[pair] < 0) return;                               // (uniform) refused by the programme
+    const int T = lengths[item], N = phoneme_lengths[query];
+    float* ct = totals + pair * frames;
+    int* cb = begins + pair * frames;
+    if (curve_total) {
+        for (int t = lane; t < T; t += 64) {
+            curve_total[pair * frames + t] = ct[t];
+            curve_begin[pair * frames + t] = cb[t];
+        }
+    }
+    int* out_begin = begin + pair * top;
+    int* out_end = end + pair * top;
+    float* out_total = total + pair * top;
+    float* out_mean = mean + pair * top;
+    int taken = 0;
+    int from = 0, to = 0;                                      // the hit of the round before: frames from .. to - 1
+    for (; taken < top; ++taken) {
+        float best = -INFINITY;
+        int at = -1;
+        for (int t0 = N - 1; t0 < T; t0 += PICK * 64) {        // (uniform)
+            int b[PICK]; float sum[PICK];
+#pragma unroll
+            for (int j = 0; j < PICK; ++j) {
+                const int t = t0 + j * 64 + lane;
+                b[j] = t < T ? cb[t] : -1;
+                sum[j] = t < T ? ct[t] : 0.f;
+            }
+#pragma unroll
+            for (int j = 0; j < PICK; ++j) {                   // in order of t: of equal means the later one stays
+                const int t = t0 + j * 64 + lane;
+                if (b[j] < 0) continue;
+                if (b[j] < to && t >= from) { cb[t] = -1; continue; }
+                const float value = sum[j] / (float)(t - b[j] + 1);
+                if (value >= best) { best = value; at = t; }
+            }
+        }
+#pragma unroll
+        for (int step = 1; step < 64; step <<= 1) {
+            const float other = __shfl_xor(best, step);
+            const int where = __shfl_xor(at, step);
+            const bool better = other > best || (other == best && where > at);
+            best = better ? other : best;
+            at = better ? where : at;
+        }
+        if (at < 0 || best < threshold) break;                 // (uniform)
+        from = cb[at];
+        to = at + 1;
+        if (lane == 0) {
+            out_begin[taken] = from;
+            out_end[taken] = to;
+            out_total[taken] = ct[at];
+            out_mean[taken] = best;
+        }
+    }
+    for (int h = taken + lane; h < top; h += 64) {
+        out_begin[h] = out_end[h] = -1;
+        out_total[h] = out_mean[h] = NAN;
+    }
+    if (lane == 0) count[pair] = taken;
+}
+
 int check_common(const char* what, const void* ppg, int frames, int items, const void* lengths) {
     if (!ppg || !lengths || items <= 0 || frames <= 0) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
     if (frames > PPG_ALIGN_MAX_FRAMES)
@@ -653,6 +862,55 @@ int ppg_decode(int device, const float* ppg, int frames, int items, const int32_
                        phonemes, starts, runs);
     const hipError_t he = hipGetLastError();
     return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "decode: %s", hipGetErrorString(he));
+}
+
+size_t ppg_search_workspace_bytes(int items, int frames, int queries) {
+    if (items <= 0 || items > PPG_SEARCH_MAX_ITEMS || frames <= 0 || frames > PPG_SEARCH_MAX_FRAMES || queries <= 0 ||
+        queries > PPG_SEARCH_MAX_QUERIES)
+        return 0;
+    return search_layout(items, frames, queries).bytes;
+}
+
+int ppg_search(int device, const float* ppg, int frames, int items, const int32_t* lengths, const int32_t* phonemes,
+               int max_phonemes, int queries, const int32_t* phoneme_lengths, int top, float threshold, int32_t* begin,
+               int32_t* end, float* total, float* mean, int32_t* count, float* curve_total, int32_t* curve_begin,
+               void* workspace, size_t workspace_bytes, void* stream) {
+    if (!ppg || !lengths || !phonemes || !phoneme_lengths || !begin || !end || !total || !mean || !count ||
+        !workspace || items <= 0 || frames <= 0 || queries <= 0 || max_phonemes <= 0)
+        return ppg::fail_message(PPG_EINVAL, "search: bad argument");
+    if (frames > PPG_SEARCH_MAX_FRAMES)
+        return ppg::fail_message(PPG_EINVAL, "search: %d frames, at most %d", frames, PPG_SEARCH_MAX_FRAMES);
+    if (items > PPG_SEARCH_MAX_ITEMS)
+        return ppg::fail_message(PPG_EINVAL, "search: %d items, at most %d per call", items, PPG_SEARCH_MAX_ITEMS);
+    if (queries > PPG_SEARCH_MAX_QUERIES)
+        return ppg::fail_message(PPG_EINVAL, "search: %d queries, at most %d per call", queries,
+                                 PPG_SEARCH_MAX_QUERIES);
+    if (max_phonemes > PPG_SEARCH_MAX_PHONEMES)
+        return ppg::fail_message(PPG_EINVAL, "search: %d phonemes, at most %d", max_phonemes, PPG_SEARCH_MAX_PHONEMES);
+    if (top < 1 || top > PPG_SEARCH_MAX_HITS)
+        return ppg::fail_message(PPG_EINVAL, "search: top = %d, must be 1 .. %d", top, PPG_SEARCH_MAX_HITS);
+    if (threshold != threshold) return ppg::fail_message(PPG_EINVAL, "search: the threshold is NaN");
+    if (!curve_total != !curve_begin)
+        return ppg::fail_message(PPG_EINVAL, "search: curve_total and curve_begin go together");
+    const SearchLayout w = search_layout(items, frames, queries);
+    if (workspace_bytes < w.bytes)
+        return ppg::fail_message(PPG_EINVAL, "search: workspace of %zu bytes, %zu needed", workspace_bytes, w.bytes);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16)
+        return ppg::fail_message(PPG_EINVAL, "search: workspace must be 16-byte aligned");
+    if (hipSetDevice(device) != hipSuccess)
+        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    float* logp = reinterpret_cast<float*>(ws + w.logp);
+    float* totals = reinterpret_cast<float*>(ws + w.totals);
+    int* begins = reinterpret_cast<int*>(ws + w.begins);
+    hipLaunchKernelGGL(align_prepare, dim3((frames + 63) / 64, items), dim3(64), 0, s, ppg, frames, lengths, logp);
+    hipLaunchKernelGGL(search_programme, dim3(queries, items), dim3(64), 0, s, logp, frames, lengths, phonemes,
+                       max_phonemes, phoneme_lengths, totals, begins, count);
+    hipLaunchKernelGGL(search_pick, dim3(queries, items), dim3(64), 0, s, frames, lengths, phoneme_lengths, top,
+                       threshold, totals, begins, begin, end, total, mean, count, curve_total, curve_begin);
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "search: %s", hipGetErrorString(he));
 }
 
 }  // extern "C"

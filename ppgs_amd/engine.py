@@ -6,6 +6,7 @@ eager-PyTorch fallback: if the library is missing or no GPU is visible the
 calls raise.
 """
 import ctypes
+import math
 import os
 import threading
 
@@ -161,6 +162,12 @@ SYMBOLS = {
     'ppg_decode': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_search_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_search': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_size_t, ctypes.c_void_p]),
     'ppg_metrics_state_bytes': (ctypes.c_size_t, []),
     'ppg_metrics_reset': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_metrics_update': (ctypes.c_int, [
@@ -793,6 +800,89 @@ def decode_items(ppg, lengths):
                 device.index, x[at:].data_ptr(), frames, min(ALIGN_MAX_ITEMS, items - at), lengths[at:].data_ptr(),
                 phonemes[at:].data_ptr(), starts[at:].data_ptr(), runs[at:].data_ptr(), stream))
     return phonemes, starts, runs
+
+
+SEARCH_MAX_FRAMES = 262144       # PPG_SEARCH_MAX_FRAMES
+SEARCH_MAX_PHONEMES = 256        # PPG_SEARCH_MAX_PHONEMES
+SEARCH_MAX_HITS = 64             # PPG_SEARCH_MAX_HITS
+SEARCH_MAX_ITEMS = 65535         # PPG_SEARCH_MAX_ITEMS, per call of the library
+SEARCH_MAX_QUERIES = 65535       # PPG_SEARCH_MAX_QUERIES, per call of the library
+SEARCH_WORKSPACE_BYTES = 1 << 30  # a larger batch runs as several calls, each within this much workspace
+
+
+def search_items(ppg, lengths, table, counts, top=1, threshold=-math.inf, want_curve=False):
+    """Phrase search (ppg_search): every query table[q, :counts[q]] in every recording ppg[b, :, :lengths[b]].
+    (items, 40, frames) on a GPU, table a padded (queries, max_phonemes) integer tensor, both lengths as host
+    integers -> begin, end (items, queries, top) int32, total, mean (items, queries, top) fp32, count (items, queries)
+    int32, and the curve: None, or (curve_total fp32, curve_begin int32), each (items, queries, frames) with -inf and
+    -1 at and past an item's own length.  Entries at or past count are -1, -1, NaN, NaN; a pair that cannot be searched
+    has count -1."""
+    if not ppg.is_cuda:
+        raise PpgError('ppgs_amd: the post-ops work on HIP device tensors')
+    x = ppg.to(torch.float32).contiguous()
+    if x.dim() != 3 or x.shape[1] != 40 or x.shape[0] < 1:
+        raise ValueError(f'PPGs must be (items >= 1, 40, frames), got {tuple(x.shape)}')
+    items, frames = x.shape[0], x.shape[2]
+    if not 1 <= frames <= SEARCH_MAX_FRAMES:
+        raise ValueError(f'search takes 1 to {SEARCH_MAX_FRAMES} frames, got {frames}')
+    lengths = [int(v) for v in lengths]
+    if len(lengths) != items:
+        raise ValueError(f'{len(lengths)} lengths for {items} items')
+    device = x.device
+    if table.dim() != 2 or table.shape[0] < 1 or not 1 <= table.shape[1] <= SEARCH_MAX_PHONEMES:
+        raise ValueError(f'queries must be (queries >= 1, 1 to {SEARCH_MAX_PHONEMES}), got {tuple(table.shape)}')
+    table = table.to(device=device, dtype=torch.int32).contiguous()
+    queries, most = table.shape
+    counts = [int(v) for v in counts]
+    if len(counts) != queries:
+        raise ValueError(f'{len(counts)} phoneme lengths for {queries} queries')
+    top, threshold = int(top), float(threshold)
+    if not 1 <= top <= SEARCH_MAX_HITS:
+        raise ValueError(f'top must be 1 to {SEARCH_MAX_HITS}, got {top}')
+    if threshold != threshold:
+        raise ValueError('the threshold is NaN')
+    lengths = torch.tensor(lengths, dtype=torch.int32).to(device)
+    counts = torch.tensor(counts, dtype=torch.int32).to(device)
+    shape = (items, queries, top)
+    begin = torch.empty(shape, dtype=torch.int32, device=device)
+    end = torch.empty(shape, dtype=torch.int32, device=device)
+    total = torch.empty(shape, dtype=torch.float32, device=device)
+    mean = torch.empty(shape, dtype=torch.float32, device=device)
+    count = torch.empty((items, queries), dtype=torch.int32, device=device)
+    curve = None
+    if want_curve:
+        curve = (torch.full((items, queries, frames), -math.inf, dtype=torch.float32, device=device),
+                 torch.full((items, queries, frames), -1, dtype=torch.int32, device=device))
+    lib = library()
+    bytes_for = lib.ppg_search_workspace_bytes
+    # queries per call: the prepared frames of one recording and as many curves as the budget holds; then recordings
+    some = max(1, min(queries, SEARCH_MAX_QUERIES, (SEARCH_WORKSPACE_BYTES // frames - 176) // 8))
+    group = max(1, min(items, SEARCH_MAX_ITEMS, SEARCH_WORKSPACE_BYTES // bytes_for(1, frames, some)))
+    size = bytes_for(group, frames, some)
+    workspace = torch.empty((size,), dtype=torch.uint8, device=device)
+    outputs = (begin, end, total, mean, count) + (curve or ())
+
+    def pointer(tensor):
+        return tensor.data_ptr() if tensor is not None else None
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for at in range(0, items, group):
+            rows = min(group, items - at)
+            for low in range(0, queries, some):
+                columns = min(some, queries - low)
+                if columns == queries:                          # the whole table: straight into the outputs
+                    parts = [out[at:] for out in outputs]
+                else:
+                    parts = [out[at:at + rows, low:low + columns].contiguous() for out in outputs]
+                slots = parts + [None] * (7 - len(parts))          # no curve: two NULL pointers
+                _check(lib.ppg_search(
+                    device.index, x[at:].data_ptr(), frames, rows, lengths[at:].data_ptr(), table[low:].data_ptr(),
+                    most, columns, counts[low:].data_ptr(), top, threshold, *[pointer(part) for part in slots],
+                    workspace.data_ptr(), size, stream))
+                if columns != queries:
+                    for out, part in zip(outputs, parts):
+                        out[at:at + rows, low:low + columns].copy_(part)
+    return begin, end, total, mean, count, curve
 
 
 METRICS_FIXED_POINT = 2.0 ** 32        # the real-valued accumulators of PpgMetricsState count units of 2^-32
