@@ -71,17 +71,34 @@ enum {
  * ppgs/model/transformer.py:15-43 (+ torch TransformerEncoderLayer defaults:
  * ffn 2048, ReLU, post-norm, eps 1e-5) and the chunking constants
  * ppgs/config/defaults.py:158-161.
+ *
+ * What ppg_engine_create accepts; anything else is refused there with
+ * PPG_EINVAL and a message that names the field -- no geometry fails later,
+ * in ppg_encode:
+ *   input_channels   >= 1 (zero-padded to whole K-groups)
+ *   hidden_channels  256 or 512, heads such that hidden / heads is 128 or 256
+ *                    (fp16x2: 256 / 128 and 512 / 256 only)
+ *   num_layers       0 .. PPG_MAX_LAYERS
+ *   ffn_channels     a multiple of 64, up to 6656 at hidden 256 and 5120 at
+ *                    hidden 512 (b1 lies in LDS beside the FFN kernel's weight
+ *                    tiles); a multiple of 256, with no upper limit, where the
+ *                    FFN runs as two GEMMs (fp16x2 at hidden 512, and any
+ *                    engine created under PPGS_AMD_FFN_UNFUSED=1)
+ *   output_channels  1 .. 48
+ *   kernel_size      5
+ *   max_positions    >= chunk_length (a window adds rows 0 .. its length - 1)
+ *   chunk_length     <= 512 and > 2 * chunk_overlap
  */
 typedef struct PpgConfig {
     int32_t input_channels;  /* 80 (mel) / 768 (w2v2fb)                       */
     int32_t hidden_channels; /* 256 / 512; multiple of 64                     */
     int32_t num_layers;      /* 5                                             */
-    int32_t ffn_channels;    /* 2048                                          */
+    int32_t ffn_channels;    /* 2048; multiple of 64, limits above            */
     int32_t output_channels; /* 40                                            */
     int32_t kernel_size;     /* 5                                             */
     int32_t heads;           /* 2; hidden/heads must be 128 or 256            */
     int32_t is_causal;       /* config/causal_transformer.py:18               */
-    int32_t max_positions;   /* 5000 rows in position.encoding                */
+    int32_t max_positions;   /* 5000 rows in position.encoding; >= chunk_length */
     int32_t chunk_length;    /* 500                                           */
     int32_t chunk_overlap;   /* 50                                            */
     int32_t precision;       /* PPG_PRECISION_*                               */

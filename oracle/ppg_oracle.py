@@ -254,29 +254,29 @@ def window_forward(state, x, clens, is_causal=False, heads=2, quant=None, dtype=
 
 
 def forward(state, features, lengths, is_causal=False, legacy_mode=False, quant=None,
-            dtype=torch.float32, mask_hook=None):
+            dtype=torch.float32, mask_hook=None, heads=2):
     """reference Transformer.forward (transformer.py:45-81) -> logits (B,40,T)."""
     features = features.to(dtype)
     T = features.shape[-1]
     if legacy_mode or T <= CHUNK_LENGTH:
-        return window_forward(state, features, lengths, is_causal, quant=quant, dtype=dtype,
+        return window_forward(state, features, lengths, is_causal, heads=heads, quant=quant, dtype=dtype,
                               mask_hook=mask_hook)
     padded = torch.nn.functional.pad(
         features, (CHUNK_OVERLAP, 0), mode='replicate')
     outputs = []
     for w in plan_windows(T, lengths):
         split = padded[..., w['start']:w['start'] + w['Tc']]
-        out = window_forward(state, split, w['clens'], is_causal, quant=quant, dtype=dtype,
+        out = window_forward(state, split, w['clens'], is_causal, heads=heads, quant=quant, dtype=dtype,
                              mask_hook=mask_hook)
         outputs.append(out[..., w['keep_lo']:w['keep_hi']])
     return torch.cat(outputs, dim=-1)
 
 
 def from_features(state, features, lengths, softmax=True, is_causal=False,
-                  legacy_mode=False, quant=None, dtype=torch.float32, mask_hook=None):
+                  legacy_mode=False, quant=None, dtype=torch.float32, mask_hook=None, heads=2):
     """reference ppgs.from_features / infer (core.py:72-128, 551-596), fp32."""
     with torch.inference_mode():
-        logits = forward(state, features, lengths, is_causal, legacy_mode, quant, dtype, mask_hook)
+        logits = forward(state, features, lengths, is_causal, legacy_mode, quant, dtype, mask_hook, heads)
         if softmax:
             return torch.softmax(logits, dim=1)
         return logits

@@ -62,7 +62,8 @@ static void choose_ffn_tiling(const PpgEngine* e, int M, int* nt_out, int* split
                        : (e->cfg.hidden_channels == 256 ? 2 : 1);
     int nt = choose_nt(e->num_cus, e->ffn_nt, M, max_nt);
     int splits = 1;
-    const int chunks = e->cfg.ffn_channels / (32768 / (e->cfg.hidden_channels * e->sz));
+    // (a workgroup of a split launch sums chunks / splits hidden chunks, ffn_body's NC: only divisors of the chunk count)
+    const int chunks = ppg::ffn_chunks(e->cfg.hidden_channels, e->cfg.ffn_channels, e->sz);
     if (e->ffn_split && e->ffn_fused && e->ffn_nt == 0) {
         const int tiles_max_nt = (M + 64 * max_nt - 1) / (64 * max_nt);
         // only when the tiles would leave 7/8 of the chip idle: the partial-sum
@@ -71,7 +72,7 @@ static void choose_ffn_tiling(const PpgEngine* e, int M, int* nt_out, int* split
         if (tiles_max_nt * 8 <= e->num_cus) {
             nt = max_nt;
             const int cap = e->ffn_split_max > 0 ? e->ffn_split_max : chunks / 2;
-            while (splits * 2 <= cap && tiles_max_nt * splits * 2 <= e->num_cus) splits *= 2;
+            while (splits * 2 <= cap && chunks % (splits * 2) == 0 && tiles_max_nt * splits * 2 <= e->num_cus) splits *= 2;
         }
     }
     // 4-byte operand modes (fp32, fp16x2) cannot hold more than 128 tokens in LDS, so a launch whose tiles
@@ -81,7 +82,7 @@ static void choose_ffn_tiling(const PpgEngine* e, int M, int* nt_out, int* split
         const int tiles = (M + 64 * max_nt - 1) / (64 * max_nt);
         auto rounds = [&](int sp) { return (double)((tiles * sp + e->num_cus - 1) / e->num_cus) / sp + 0.08 * (sp > 1 ? 1 + 0.5 * sp : 0); };
         int best = 1;
-        for (int sp = 2; sp <= 4 && sp <= chunks / 2; sp *= 2)
+        for (int sp = 2; sp <= 4 && sp <= chunks / 2 && chunks % sp == 0; sp *= 2)
             if (rounds(sp) < rounds(best)) best = sp;
         if (best > 1) { nt = max_nt; splits = best; }
     }
@@ -307,9 +308,25 @@ int ppg_engine_create(const PpgConfig* cfg, const PpgWeights* wts, int device, P
     if (C < 1) return fail(PPG_EINVAL, "input_channels %d", C);
     if (cfg->chunk_length <= 2 * cfg->chunk_overlap || cfg->chunk_length > 512)
         return fail(PPG_EINVAL, "chunk_length %d / overlap %d unsupported", cfg->chunk_length, cfg->chunk_overlap);
+    // a window adds the table's rows 0 .. its length - 1 to its frames (never more than chunk_length of them outside legacy mode,
+    // where build_plan holds the frames below max_positions)
+    if (cfg->max_positions < cfg->chunk_length)
+        return fail(PPG_EINVAL, "max_positions %d below chunk_length %d: a window would read position rows behind the table", cfg->max_positions, cfg->chunk_length);
     if (!known_precision(cfg->precision)) return fail(PPG_EINVAL, "precision %d", cfg->precision);
     if (cfg->precision == PPG_PRECISION_FP16X2 && !((H == 256 && dh == 128) || (H == 512 && dh == 256)))
         return fail(PPG_EINVAL, "the fp16x2 mode covers hidden 256 with head dimension 128 and hidden 512 with head dimension 256 (hidden %d, head dimension %d)", H, dh);
+    {   // What the FFN routes can do with this F is settled here, not at the first launch (and before the device is touched).
+        // The FFN runs as two GEMMs in the fp16x2 mode at hidden 512 and under PPGS_AMD_FFN_UNFUSED, 256 hidden features per
+        // pass of the first; everywhere else the fused kernel must hold b1 in LDS beside its weight tiles.
+        const bool split = cfg->precision == PPG_PRECISION_FP16X2;
+        const bool two_gemm = split ? H == 512 : ppg::env_switch("PPGS_AMD_FFN_UNFUSED", 0) != 0;
+        if (two_gemm && F % 256)
+            return fail(PPG_EINVAL, "ffn_channels %d must be a multiple of 256 for the two-GEMM FFN (%s)", F,
+                        split ? "the only route of the fp16x2 mode at hidden 512" : "PPGS_AMD_FFN_UNFUSED");
+        if (!two_gemm && !ppg::ffn_fits(H, F, false))
+            return fail(PPG_EINVAL, "ffn_channels %d above %d, the most the FFN kernel holds in LDS at hidden %d", F,
+                        (int)((ppg::kLdsBytes - ppg::ffn_lds_bytes(H, 0, 6)) / 4 / 64 * 64), H);
+    }
     if (int rc = use_device(device, "PPG engine")) return rc;
 
     std::unique_ptr<PpgEngine> e(new PpgEngine());
@@ -369,8 +386,17 @@ int ppg_engine_create(const PpgConfig* cfg, const PpgWeights* wts, int device, P
         // kernel cannot hold a 32-wide hidden group of both weight tiles: ppg_kernels.hip, launch_linear_x2_nt)
         if (H == 512) e->ffn_fused = false;
     }
+    // With the out-projection (or the mixed tiling's hand-off) fused in, the FFN kernel has LDS for fewer hidden
+    // features: those fusions are switched off where they do not fit (an F that fits no form was refused above).
+    if (e->ffn_fused) {
+        if (!ppg::ffn_fits(H, F, true)) e->op_fused = false;
+        if (!ppg::ffn_mixed_fits(H, F)) e->ffn_mixed = false;
+        if (e->ffn_splits_forced > 0 && ppg::ffn_chunks(H, F, e->sz) % e->ffn_splits_forced)
+            return fail(PPG_EINVAL, "PPGS_AMD_FFN_SPLITS=%d does not divide the %d hidden chunks of ffn_channels %d", e->ffn_splits_forced,
+                        ppg::ffn_chunks(H, F, e->sz), F);
+    }
     if (!e->layer32 || H != 256 || e->Cp != 96 || !e->qkv_fused) e->head32 = false;
-    if (e->sz != 2 || (H != 256 && H != 512) || F % 128 || F > 6656) e->layer32 = false;
+    if (e->sz != 2 || (H != 256 && H != 512) || F % 128 || F > ppg::layer32_max_ffn(H)) e->layer32 = false;
 #ifdef PPG_LIN_TIMING
     if (const char* v = getenv("PPGS_AMD_LIN_TIMING")) {
         e->lin_dbg_class = atoi(v);

@@ -234,6 +234,17 @@ void dump_timing_stamps(const PpgEngine* e);   // ppg_timing.hip: what the engin
 #endif
 
 int choose_nt(int num_cus, int forced_nt, int M, int max_nt);
+// The fused FFN kernel (ppg_kernels.hip, ffn_body) walks the hidden features in chunks of one 32 KiB W1 tile; a
+// split-hidden launch gives each of its `splits` workgroups per tile chunks / splits of them, so a split count must
+// divide the chunk count.
+inline int ffn_chunks(int hidden, int ffn, int sz) { return ffn / (32768 / (hidden * sz)); }
+// Dynamic LDS of the fused FFN kernel (launch_ffn_t): the weight tiles, b1 and 6 parameter rows of `hidden` floats --
+// 9 with the out-projection or the Q/K/V tail fused in; the mixed tiling (launch_ffn_mixed) adds a 16 KiB hand-off to
+// the 6.  160 KiB per workgroup on gfx950.
+constexpr size_t kLdsBytes = 163840;
+inline size_t ffn_lds_bytes(int hidden, int ffn, int rows) { return 131072 + (size_t)ffn * 4 + (size_t)rows * hidden * 4; }
+inline bool ffn_fits(int hidden, int ffn, bool op) { return ffn_lds_bytes(hidden, ffn, op ? 9 : 6) <= kLdsBytes; }
+inline bool ffn_mixed_fits(int hidden, int ffn) { return ffn_lds_bytes(hidden, ffn, 6) + 16384 <= kLdsBytes; }
 Workspace layout(const PpgEngine* e, int tokens, int vt_tokens);
 // Queries per attention workgroup of a KV-cached stream's steps: half a tile at head dimension 128 (its items are narrow)
 inline int stream_query_tile(int head_dim) { return head_dim == 128 ? attn_query_tile(head_dim) / 2 : attn_query_tile(head_dim); }

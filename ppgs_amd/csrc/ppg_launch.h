@@ -51,6 +51,7 @@ bool ffn32x2_supported(int H, int F);     // what launch_ffn32x2 accepts: the en
 bool outconv_supported(int precision, const LinearArgs& a);
 hipError_t launch_outconv(int precision, const LinearArgs& a, hipStream_t s);
 int layer32_tokens(int hidden);       // token rows per workgroup (160 at hidden 256, 96 at hidden 512)
+int layer32_max_ffn(int hidden);      // the largest F whose b1 fits in LDS beside the tile (6656 at hidden 256, 4864 at hidden 512)
 // wav2vec2 feature encoder, layer 0 (conv k10 s5 + GroupNorm + GELU; ppg_w2v2.hip) and the fp32 read-out of the last layer
 hipError_t launch_w2v2_layer0(int precision, const float* audio, int batch, long samples, long frames, int rows_per_item,
                               const float* w0, const float* gamma, const float* beta, double* moments, float2* scale_shift,

@@ -697,6 +697,9 @@ namespace ppg {
 
 int layer32_tokens(int hidden) { return hidden == 512 ? Geo<512>::TOKS : Geo<256>::TOKS; }
 
+// b1 lies behind everything else in LDS (Geo::L_B1): the whole chunks of F that leave it inside 160 KiB
+int layer32_max_ffn(int hidden) { return (163840 - (hidden == 512 ? Geo<512>::L_B1 : Geo<256>::L_B1)) / 4 / HC * HC; }
+
 hipError_t launch_layer32(int precision, const Layer32Args& a, hipStream_t s) {
     if (precision == PPG_PRECISION_BF16) return launch_layer32_p<PrecBF16>(a, s);
     if (precision == PPG_PRECISION_FP16) return launch_layer32_p<PrecF16>(a, s);

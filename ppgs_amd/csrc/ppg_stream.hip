@@ -99,12 +99,12 @@ int ppg_stream_create_batch(PpgEngine* e, int batch, int max_frames, int feature
     st->vt_bytes = align_up((size_t)c.hidden_channels * st->ws.vt_ld * e->sz, 256);
     // partial sums of the split-hidden FFN launches: [splits][batch * R][H] fp32, at most 256 MiB
     {
-        const int chunks = c.ffn_channels / (32768 / (c.hidden_channels * e->sz));
+        const int chunks = ppg::ffn_chunks(c.hidden_channels, c.ffn_channels, e->sz);    // (a split count must divide them)
         // (under a row map a split's rows are slot-dense, ceil(map_blocks / 4) * 64 of them -- ppg_kernels.hip, ffn_body's
         // epilogue and the reduce pass: up to MT rounded up to a whole 64-row workgroup, not MT)
         const size_t per_split = (size_t)round_up(MT, 64) * c.hidden_channels * 4;
         st->max_splits = 1;
-        while (st->max_splits * 2 <= std::max(1, chunks / 2) && (size_t)(st->max_splits * 2) * per_split <= ((size_t)256 << 20)) st->max_splits *= 2;
+        while (st->max_splits * 2 <= std::max(1, chunks / 2) && chunks % (st->max_splits * 2) == 0 && (size_t)(st->max_splits * 2) * per_split <= ((size_t)256 << 20)) st->max_splits *= 2;
         st->part_off = align_up(st->ws.total, 256);
         st->cache_off = align_up(st->part_off + (st->max_splits > 1 ? st->max_splits * per_split : 0), 256);
     }

@@ -323,6 +323,8 @@ class Engine:
                 'ppgs_amd: no HIP device visible; the engine has no CPU path')
         lib = library()
         cin, hidden, layers = weights.geometry(state)
+        if layers > PPG_MAX_LAYERS:     # (PpgWeights has that many slots per parameter: refused before they are filled)
+            raise ValueError(f'ppgs_amd: num_layers {layers} outside [0,{PPG_MAX_LAYERS}]')
         self.input_channels = cin
         self.hidden_channels = hidden
         self.output_channels = state['output_layer.weight'].shape[0]

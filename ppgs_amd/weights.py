@@ -82,6 +82,9 @@ def seeded_state_dict(
     hidden_channels=config.HIDDEN_CHANNELS,
     num_layers=config.NUM_HIDDEN_LAYERS,
     sharpen=1.0,
+    output_channels=config.OUTPUT_CHANNELS,
+    ffn_channels=config.FFN_CHANNELS,
+    max_len=config.MAX_POSITIONS,
 ):
     """Deterministic synthetic checkpoint in the reference layout.
 
@@ -93,13 +96,20 @@ def seeded_state_dict(
     initialisation has every such parameter at exactly 0 or 1.
     ``sharpen`` scales every matrix: >1 gives peakier posteriors so that a
     1e-4 tolerance on probabilities is discriminating.
+    ``output_channels``, ``ffn_channels`` and ``max_len`` (the rows of the
+    position table) give the other geometries the engine accepts; the draws
+    are made key by key in the order of :func:`state_dict_shapes`, so the
+    defaults give the tensors they always gave.
     """
     generator = torch.Generator(device='cpu')
     generator.manual_seed(seed)
     shapes = state_dict_shapes(
         input_channels=input_channels,
         hidden_channels=hidden_channels,
-        num_layers=num_layers)
+        num_layers=num_layers,
+        output_channels=output_channels,
+        ffn_channels=ffn_channels,
+        max_len=max_len)
     state = {}
     for key, shape in shapes.items():
         if key == 'position.encoding':
