@@ -629,6 +629,84 @@ int ppg_search(int device, const float* ppg, int frames, int items, const int32_
                int32_t* curve_begin, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Live phrase search: ppg_search carried across the pushes of a stream (keyword spotting on a live PPG, e.g. the
+ * frames an audio stream emits).  A push does work proportional to its own frames, whatever the age of the stream.
+ * Not in the reference.
+ *
+ * One pair is a stream of posterior frames and a query s[0 .. N-1], 1 <= N <= PPG_SEARCH_MAX_PHONEMES.  A stream has a
+ * position p, the number of frames received since its last reset.  Frame indices are absolute: they count from the
+ * reset.
+ *   Curve.  ppg_search's recurrence, unchanged: the same prepared frame, the same emission r = logp[s[n]] - m, the same
+ *   strict comparisons, the same fp32 additions in frame order, and a fresh origin 0 with b = t at every frame, t the
+ *   absolute frame index.  A push of F frames at position p computes curve_total[p .. p+F-1] and curve_begin[p .. p+F-1]
+ *   from the saved (D, b) of every state, and saves them again.  For any split of a recording into pushes the
+ *   concatenated curve equals ppg_search's curve of the recording bit for bit, lengths 0 and 1 included.
+ *   Online detector.  Per pair: threshold (fp32, may be -inf, never NaN) and patience (frames, >= 0).  Its state is
+ *   `taken`, the exclusive end of the last emitted hit, initially 0, and at most one pending hit (begin, end, total,
+ *   mean).  For each frame t in order, after its curve values exist:
+ *     1. If there is a pending hit and t - (pending.end - 1) > patience, it is emitted: taken = pending.end, and nothing
+ *        is pending.
+ *     2. Let b = curve_begin[t].  If b >= 0 and b >= taken, mean = curve_total[t] / float(t - b + 1), one fp32 division
+ *        as in ppg_search.  If mean >= threshold, frame t is a candidate (b, t + 1, curve_total[t], mean):
+ *          with no pending hit the candidate becomes pending;
+ *          if b < pending.end (the spans overlap) the candidate replaces the pending hit when mean >= pending.mean:
+ *          ties go to the later end frame, as in ppg_search;
+ *          otherwise the spans are disjoint: the pending hit is emitted, taken = pending.end, and the candidate becomes
+ *          pending.
+ *   flush emits the pending hit, if any, and sets taken; the curve state and the position are kept.  reset returns a
+ *   stream to position 0 with every state at -inf / -1, taken = 0 and nothing pending.  Emitted hits are disjoint, come
+ *   in stream order, and do not depend on how the frames were split into pushes.
+ *
+ * The caller owns the state (device memory, 16-byte aligned, ppg_search_stream_state_bytes(streams, queries,
+ * max_phonemes) bytes, to be reset before its first push); there is no handle.  Four blocks, each 256-byte aligned: the
+ * position of every stream (int32), the detector of every pair (8 words: taken, the pending begin or -1, end, total,
+ * mean, hits emitted since the reset, 2 spare), then D and b of every pair (64 words each where max_phonemes <= 64, 256
+ * above: the strips of a whole wave).  A state belongs to one (streams, queries, max_phonemes) and one query table.
+ *
+ * ppg_search_stream_push: every stream takes lengths[i] frames; every query runs on every stream.
+ *   ppg             : device fp32 (streams, 40, frames), padded; frames at or past a stream's length are never read
+ *   lengths         : device int32[streams], each in [0, frames]; a stream with 0 sits out the step
+ *   phonemes, max_phonemes, queries, phoneme_lengths : as ppg_search
+ *   threshold, patience : as above; cap >= 1 is the number of event slots per pair
+ *   begin, end      : device int32 (streams, queries, cap)
+ *   total, mean     : device fp32 (streams, queries, cap)
+ *   count           : device int32 (streams, queries): the events emitted in this push, in stream order.  Only the first
+ *                     min(count, cap) are written, so count > cap says that the push overflowed (as snprintf does);
+ *                     slots at or past count are begin = end = -1, total = mean = NaN.  A pair that cannot be pushed (N
+ *                     outside [1, max_phonemes], a phoneme index outside 0 .. 39, a length outside [0, frames], a
+ *                     position that would pass INT32_MAX) gets count = -1: its state and its other outputs are left
+ *                     untouched, its stream's position stays if the length or the position is at fault, and nothing is
+ *                     accessed out of range.
+ *   curve_total     : device fp32 (streams, queries, frames) or NULL; entries t < lengths[i] are written: the curve of
+ *                     the pushed frames
+ *   curve_begin     : device int32 (streams, queries, frames) or NULL, both or neither; absolute begins
+ *   workspace       : device memory, 16-byte aligned, at least ppg_search_stream_workspace_bytes(streams, frames,
+ *                     queries) bytes: the prepared frames of this push (176 B per frame)
+ * ppg_search_stream_flush: begin, end, total, mean, count are (streams, queries): count is 1 and the hit is written where
+ * one was pending, else 0 and -1, -1, NaN, NaN.  ppg_search_stream_reset and _flush take `which`, device
+ * int32[streams] flags of the streams meant, or NULL for all; the other streams keep their state (and flush gives them
+ * count = 0).
+ * Kernel launches on `stream` only: no allocation, synchronisation or copy.  Every workspace byte read was written
+ * earlier in the same call.  Every pair's results are a function of its own stream and query alone.  The position of a
+ * stream is advanced once per push by a launch of its own after the pairs have run.
+ * PPG_EINVAL, and nothing launched, for: a NaN threshold, patience < 0, cap < 1, frames outside
+ * 1 .. PPG_SEARCH_MAX_FRAMES, a limit of ppg_search exceeded (streams count as its items), one curve pointer without the
+ * other, an unaligned or short workspace, an unaligned state, a NULL state, input or output.
+ * The two *_bytes helpers are host-only and return 0 for impossible arguments.
+ */
+size_t ppg_search_stream_state_bytes(int streams, int queries, int max_phonemes);
+size_t ppg_search_stream_workspace_bytes(int streams, int frames, int queries);
+int ppg_search_stream_reset(int device, void* state, int streams, int queries, int max_phonemes, const int32_t* which,
+                            void* stream);
+int ppg_search_stream_push(int device, void* state, const float* ppg, int frames, int streams, const int32_t* lengths,
+                           const int32_t* phonemes, int max_phonemes, int queries, const int32_t* phoneme_lengths,
+                           float threshold, int patience, int cap, int32_t* begin, int32_t* end, float* total,
+                           float* mean, int32_t* count, float* curve_total, int32_t* curve_begin, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int ppg_search_stream_flush(int device, void* state, int streams, int queries, int max_phonemes, const int32_t* which,
+                            int32_t* begin, int32_t* end, float* total, float* mean, int32_t* count, void* stream);
+
+/*
  * Frame metrics accumulated on the device: what the reference's `python -m ppgs.evaluate` computes per batch with
  * five metric objects (ppgs/evaluate/metrics.py: Accuracy, CategoricalAccuracy, JensenShannon, TopKAccuracy, Loss,
  * DistanceMatrix), here ONE kernel launch per batch into one device block, no host synchronisation, read once at

@@ -60,6 +60,13 @@ mean); hits are disjoint and listed in the order taken.  Entries past `count` ar
     for start, end, total, mean in ppgs_amd.alignment.hit_segments(hits): ...
     b, e = int(hits.begin[0]), int(hits.end[0])
     inside = ppgs_amd.alignment.forced(ppg[:, b:e], ['hh', 'ah', 'l', 'ow'])     # the phoneme boundaries inside a hit
+
+Live phrase search (`SearchStream`, ppg_search_stream_*): the same curve carried across the pushes of a stream, bit for
+bit whatever the push sizes, with an online rule that gives a hit out once nothing later can overlap and beat it.
+
+    spotter = ppgs_amd.alignment.SearchStream(['hh', 'ah', 'l', 'ow'], threshold=-1., patience=25)
+    hits = spotter.push(frames)          # (40, k) as a stream emits them, k >= 0; Hits of this push
+    last = spotter.flush()
 """
 import collections
 import math
@@ -348,6 +355,19 @@ def decode(ppg, lengths=None):
     return Decoding([phonemes[b, :r] for b, r in enumerate(runs)], [starts[b, :r + 1] for b, r in enumerate(runs)])
 
 
+def _queries(phonemes):
+    """The queries of a search, one sequence or a list of them: (several, list of checked index lists)."""
+    several = isinstance(phonemes, (list, tuple)) and len(phonemes) > 0 and all(
+        torch.is_tensor(item) or isinstance(item, (list, tuple)) for item in phonemes)
+    sequences = [_sequence(item) for item in phonemes] if several else [_sequence(phonemes)]
+    for sequence in sequences:
+        if len(sequence) < 1:
+            raise ValueError('an empty phoneme sequence cannot be searched for')
+        if len(sequence) > SEARCH_MAX_PHONEMES:
+            raise ValueError(f'search takes at most {SEARCH_MAX_PHONEMES} phonemes per query, got {len(sequence)}')
+    return several, sequences
+
+
 def search(ppg, phonemes, lengths=None, top=1, threshold=None, curve=False):
     """Find where `phonemes` is said in `ppg`: Hits(phonemes, begin, end, total, mean, count, curve).
 
@@ -365,14 +385,7 @@ def search(ppg, phonemes, lengths=None, top=1, threshold=None, curve=False):
     if not batched and lengths is not None:
         raise ValueError('lengths go with a batch: slice a single PPG instead')
     lengths = _lengths(lengths, batch, frames)
-    several = isinstance(phonemes, (list, tuple)) and len(phonemes) > 0 and all(
-        torch.is_tensor(item) or isinstance(item, (list, tuple)) for item in phonemes)
-    sequences = [_sequence(item) for item in phonemes] if several else [_sequence(phonemes)]
-    for sequence in sequences:
-        if len(sequence) < 1:
-            raise ValueError('an empty phoneme sequence cannot be searched for')
-        if len(sequence) > SEARCH_MAX_PHONEMES:
-            raise ValueError(f'search takes at most {SEARCH_MAX_PHONEMES} phonemes per query, got {len(sequence)}')
+    several, sequences = _queries(phonemes)
     if isinstance(top, bool) or not isinstance(top, int) or not 1 <= top <= SEARCH_MAX_HITS:
         raise ValueError(f'top must be an integer from 1 to {SEARCH_MAX_HITS}, got {top!r}')
     threshold = -math.inf if threshold is None else float(threshold)
@@ -393,6 +406,166 @@ def search(ppg, phonemes, lengths=None, top=1, threshold=None, curve=False):
     names = [table[q, :n] for q, n in enumerate(counts)]
     return Hits(names if several else names[0], drop(begin), drop(end), drop(total), drop(mean), drop(count),
                 None if curves is None else (drop(curves[0]), drop(curves[1])))
+
+
+class SearchStream:
+    """`search` on a live stream: the frames come a few at a time (`Engine.stream`, `Engine.audio_stream`, ...), the
+    search is carried across the pushes on the device, and hits come out as soon as they are final.
+
+        spotter = ppgs_amd.alignment.SearchStream(['hh', 'ah', 'l', 'ow'], threshold=-1.)
+        for piece in pieces:                                     # each (40, k), k >= 0
+            hits = spotter.push(piece)
+            for start, end, total, mean in ppgs_amd.alignment.hit_segments(hits): ...
+        last = spotter.flush()
+
+    `phonemes` is one sequence or a list of Q sequences, as in `search`.  The curve is `search`'s: whatever the sizes
+    of the pushes, the pushed frames' curve values are those of `search(whole recording, ..., curve=True)` at the same
+    frames, bit for bit; frame indices count from the last reset.  Hits are decided online.  Per query the detector
+    keeps `taken`, the end of the last hit it gave out (0 at first), and at most one pending hit.  At every frame t, in
+    order: (1) a pending hit whose last frame lies more than `patience` frames back is given out; (2) if the match
+    ending at t begins at or after `taken` and its mean = curve_total[t] / (t - curve_begin[t] + 1) >= `threshold`, it
+    is a candidate: it becomes pending if nothing is; if it overlaps the pending hit it replaces it when its mean is
+    at least as large (ties go to the later end); if it is disjoint, the pending hit is given out and the candidate
+    becomes pending.  So hits are disjoint, come in stream order, and do not depend on how the frames were split.
+    `threshold` has no default: no value is sensible for every model.  `patience` = 25 frames is a quarter of a second.
+
+    `batch=None` is one stream: push((40, F)).  `batch=B` is B streams side by side: push((B, 40, Fmax), lengths),
+    lengths[b] in [0, Fmax] (None: Fmax each); a stream with 0 sits out the step and the padding is never read.
+    push returns `Hits` whose begin, end (int32), total and mean (fp32) are device tensors (B, Q, cap) with
+    cap = F // (the shortest query) + 2, more than a push can give out; count (B, Q) is the number given out in this
+    push; entries at or past it are -1, -1, NaN, NaN; with `curve` the last field is the pushed frames'
+    (curve_total, curve_begin), each (B, Q, F), else None.  The B axis is dropped for one stream and the Q axis for
+    one sequence, as in `search`, so `hit_segments` takes the result as it is.  A push of no frames (F = 0) returns
+    empty tensors and calls nothing.  flush(item=None) gives out the pending hits (cap = 1) of every stream or of
+    stream `item`; reset(item=None) starts every stream, or that one, again at frame 0.  `position` is the host list
+    of the frames each stream has received.  Nothing here waits for the device; the state and a workspace that only
+    grows belong to the object and live on `device` (None: the device of the first push's tensor, else the current
+    one)."""
+
+    def __init__(self, phonemes, threshold, patience=25, batch=None, curve=False, device=None):
+        self._several, sequences = _queries(phonemes)
+        threshold = float(threshold)
+        if math.isnan(threshold):
+            raise ValueError('the threshold is NaN')
+        if isinstance(patience, bool) or not isinstance(patience, int) or not 0 <= patience <= 2 ** 31 - 1:
+            raise ValueError(f'patience must be a number of frames from 0 to {2 ** 31 - 1}, got {patience!r}')
+        if batch is not None and (isinstance(batch, bool) or not isinstance(batch, int) or
+                                  not 1 <= batch <= engine.SEARCH_MAX_ITEMS):
+            raise ValueError(f'batch must be None or 1 to {engine.SEARCH_MAX_ITEMS} streams, got {batch!r}')
+        self.threshold, self.patience, self.batch, self.curve = threshold, patience, batch, bool(curve)
+        self._streams = 1 if batch is None else batch
+        self._counts = [len(sequence) for sequence in sequences]
+        self._most = max(self._counts)
+        self._host_table = torch.tensor([sequence + [-1] * (self._most - len(sequence)) for sequence in sequences],
+                                        dtype=torch.int32)
+        self._gpu = device
+        self._position = [0] * self._streams
+        self._state = self._workspace = self._table = self._device_counts = self._names = None
+        self._uniform, self._flags = {}, {}
+
+    @property
+    def position(self):
+        return list(self._position)
+
+    def _ensure(self, tensor=None):
+        """The device side, made at the first call that needs it."""
+        if self._state is None:
+            device = core.device_for(self._gpu, tensor)
+            self._table = self._host_table.to(device)
+            self._device_counts = torch.tensor(self._counts, dtype=torch.int32).to(device)
+            self._names = [self._table[q, :n] for q, n in enumerate(self._counts)]
+            with torch.cuda.device(device):
+                self._state = engine.search_stream_state(device, self._streams, len(self._counts), self._most)
+        return self._state.device
+
+    def _drop(self, tensor):
+        tensor = tensor if self._several else tensor[:, 0]
+        return tensor if self.batch is not None else tensor[0]
+
+    def _hits(self, begin, end, total, mean, count, curves=None):
+        return Hits(self._names if self._several else self._names[0], self._drop(begin), self._drop(end),
+                    self._drop(total), self._drop(mean), self._drop(count),
+                    None if curves is None else (self._drop(curves[0]), self._drop(curves[1])))
+
+    def _which(self, item):
+        """The flags of `item` for flush and reset: None for every stream."""
+        if item is None:
+            return None
+        if isinstance(item, bool) or not isinstance(item, int) or not 0 <= item < self._streams:
+            raise ValueError(f'item must be None or a stream index below {self._streams}, got {item!r}')
+        device = self._ensure()
+        if item not in self._flags:
+            self._flags[item] = torch.tensor([int(b == item) for b in range(self._streams)], dtype=torch.int32).to(device)
+        return self._flags[item]
+
+    def push(self, ppg, lengths=None):
+        if not torch.is_tensor(ppg) or ppg.dim() != (2 if self.batch is None else 3):
+            raise ValueError(f'a push takes {"(40, frames)" if self.batch is None else f"({self.batch}, 40, frames)"}, '
+                             f'got {tuple(getattr(ppg, "shape", ()))}')
+        if ppg.shape[-2] != config.OUTPUT_CHANNELS:
+            raise ValueError(f'PPG must have {config.OUTPUT_CHANNELS} channels, got {tuple(ppg.shape)}')
+        if self.batch is not None and ppg.shape[0] != self.batch:
+            raise ValueError(f'a push takes {self.batch} streams, got {ppg.shape[0]}')
+        frames = ppg.shape[-1]
+        if frames > SEARCH_MAX_FRAMES:
+            raise ValueError(f'a push takes at most {SEARCH_MAX_FRAMES} frames, got {frames}')
+        if lengths is None:
+            own = [frames] * self._streams
+        else:
+            if self.batch is None:
+                raise ValueError('lengths go with a batch of streams: slice a single PPG instead')
+            if torch.is_tensor(lengths):
+                lengths = lengths.detach().cpu().reshape(-1).tolist()
+            own = [int(value) for value in (lengths if isinstance(lengths, (list, tuple)) else [lengths])]
+            if len(own) != self._streams:
+                raise ValueError(f'lengths has {len(own)} entries for {self._streams} streams')
+            for value in own:
+                if not 0 <= value <= frames:
+                    raise ValueError(f'lengths: {value} is outside [0, {frames}]')
+        for position, value in zip(self._position, own):
+            if position + value > 2 ** 31 - 1:
+                raise ValueError(f'a stream takes at most {2 ** 31 - 1} frames between resets, got {position} + {value}')
+        device = self._ensure(ppg)
+        queries = len(self._counts)
+        if frames == 0:
+            shape = (self._streams, queries, 0)
+            return self._hits(
+                torch.empty(shape, dtype=torch.int32, device=device), torch.empty(shape, dtype=torch.int32, device=device),
+                torch.empty(shape, dtype=torch.float32, device=device),
+                torch.empty(shape, dtype=torch.float32, device=device),
+                torch.zeros(shape[:2], dtype=torch.int32, device=device),
+                (torch.empty(shape, dtype=torch.float32, device=device),
+                 torch.empty(shape, dtype=torch.int32, device=device)) if self.curve else None)
+        x = ppg.to(device=device, dtype=torch.float32).contiguous()
+        x = x if self.batch is not None else x[None]
+        if lengths is None:
+            if frames not in self._uniform:
+                if len(self._uniform) >= 64:                             # (a stream pushes a few sizes over and over)
+                    self._uniform.clear()
+                self._uniform[frames] = torch.full((self._streams,), frames, dtype=torch.int32, device=device)
+            on_device = self._uniform[frames]
+        else:                                                            # through pinned memory: the copy does not wait
+            on_device = torch.tensor(own, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
+        need = engine.library().ppg_search_stream_workspace_bytes(self._streams, frames, queries)
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty((need,), dtype=torch.uint8, device=device)
+        cap = frames // min(self._counts) + 2
+        begin, end, total, mean, count, curves = engine.search_stream_push(
+            self._state, x, on_device, self._table, self._device_counts, self.threshold, self.patience, cap,
+            self._workspace, self.curve)
+        self._position = [position + value for position, value in zip(self._position, own)]
+        return self._hits(begin, end, total, mean, count, curves)
+
+    def flush(self, item=None):
+        which = self._which(item)
+        self._ensure()
+        return self._hits(*engine.search_stream_flush(self._state, self._streams, len(self._counts), self._most, which))
+
+    def reset(self, item=None):
+        which = self._which(item)
+        self._ensure()
+        engine.search_stream_reset(self._state, self._streams, len(self._counts), self._most, which)
+        self._position = [0 if item is None or b == item else position for b, position in enumerate(self._position)]
 
 
 def hit_segments(hits, sample_rate=config.SAMPLE_RATE, hopsize=config.HOPSIZE):

@@ -1,5 +1,6 @@
 // Forced alignment of a PPG to a phoneme sequence with goodness-of-pronunciation scores, and the free-running
-// run-length decode, on the device.  Phrase search (ppg_search) stands at the end.
+// run-length decode, on the device.  Phrase search (ppg_search) stands at the end, and after
+// it the same search carried across the pushes of a stream (ppg_search_stream_*).
 //
 //   e[t, n] = logf(min(max(P[s[n], t], 1e-8), 1 - 1e-8))                      (the clamp of ppg_distance)
 //   D[0, 0] = e[0, 0];  D[0, n > 0] = -inf
@@ -760,6 +761,309 @@ __global__ __launch_bounds__(64) void search_pick(int frames, const int* __restr
     if (lane == 0) count[pair] = taken;
 }
 
+// ---- live phrase search (ppg_search_stream_*) ----
+//
+// The search above carried across pushes of a stream.  One pair is a stream of posterior frames and a query
+// s[0 .. N-1], 1 <= N <= 256.  A stream has a position p, the number of frames received since its last reset; frame
+// indices are absolute: they count from the reset.
+//   Curve: the recurrence above, unchanged: the same prepared frame (align_prepare, shared), the same emission
+//   r = logp[s[n]] - m, the same strict comparisons, the same fp32 additions in frame order, a fresh origin 0 with b = t
+//   at every frame, t the absolute frame index.  A push of F frames at position p computes curve_total[p .. p+F-1] and
+//   curve_begin[p .. p+F-1] from the saved (d, b) of every state and saves them again: for any split of a recording into
+//   pushes the concatenated curve equals the whole-recording curve bit for bit.
+//   Online detector, per pair: threshold (fp32, may be -inf, never NaN) and patience (frames, >= 0); its state is
+//   `taken`, the exclusive end of the last emitted hit (initially 0), and at most one pending hit (begin, end, total,
+//   mean).  For each frame t in order, after its curve values exist:
+//     1. a pending hit with t - (pending.end - 1) > patience is emitted: taken = pending.end, nothing is pending.
+//     2. b = curve_begin[t]; if b >= 0 and b >= taken, mean = curve_total[t] / float(t - b + 1) (one fp32 division, as
+//        in search_pick); if mean >= threshold, frame t is a candidate (b, t + 1, curve_total[t], mean):
+//          nothing pending: the candidate becomes pending;
+//          b < pending.end (the spans overlap): the candidate replaces the pending hit when mean >= pending.mean
+//          (ties go to the later end frame, as in search_pick);
+//          otherwise the spans are disjoint: the pending hit is emitted, taken = pending.end, the candidate is pending.
+//   flush emits the pending hit, if any, and sets taken; the curve state and the position are kept.  reset returns a
+//   stream to position 0, every state -inf / -1, taken = 0 and nothing pending.  Emitted hits are disjoint, come in
+//   stream order and do not depend on how the frames were split into pushes.
+// The caller owns the state: four blocks, each 256-byte aligned: the position of every stream (int32), the detector of
+// every pair (8 words), then d and b of every pair: a whole wave's strips each, 64 words where max_phonemes <= 64 and
+// 256 above, so that a strip is loaded and stored without a mask.  Four kernels beside align_prepare:
+//   search_stream_programme  grid (queries, streams), one wave per pair: the frame loop of search_strips (the same
+//                            staging, gather and strips) between a load and a store of the strip; the origin's begin is
+//                            position + t; the detector runs in the lane of state N-1, in registers, right after that
+//                            lane has the frame's two curve values, and stores an event only when it emits one.
+//   search_stream_advance    one thread per stream, after the programme: position += length.  The only writer of a
+//                            position in a push, so no pair sees it half-done.
+//   search_stream_flush      one thread per pair.
+//   search_stream_reset      grid (queries, streams), lanes stride over the states.
+
+struct StreamLayout {
+    size_t positions, detectors, totals, begins, bytes;        // byte offsets into the state
+};
+
+constexpr int DETECTOR = 8;                   // words of a pair's detector
+struct Detector {
+    int taken, begin, end;                    // begin = -1: nothing is pending
+    float total, mean;
+    int events;                               // hits emitted since the reset
+    int reserved[2];
+};
+static_assert(sizeof(Detector) == DETECTOR * 4, "the detector is 8 words");
+
+// the saved states of a pair: every lane's strip, for the longest strip a query of this table may have
+__host__ __device__ inline int stream_states(int max_phonemes) { return max_phonemes <= 64 ? 64 : 256; }
+
+// (65535 x 65535 pairs of 256 states are 4.4e12 bytes per block: inside a size_t)
+inline StreamLayout stream_layout(int streams, int queries, int max_phonemes) {
+    StreamLayout w{};
+    const size_t pairs = (size_t)streams * queries, states = stream_states(max_phonemes);
+    size_t at = 0;
+    w.positions = at; at = align256(at + (size_t)streams * sizeof(int));
+    w.detectors = at; at = align256(at + pairs * sizeof(Detector));
+    w.totals = at; at = align256(at + pairs * states * sizeof(float));
+    w.begins = at; at = align256(at + pairs * states * sizeof(int));
+    w.bytes = at;
+    return w;
+}
+
+// What a pair hands to its detector and gets back: the outputs of one push.
+struct Events {
+    int* begin; int* end; float* total; float* mean;           // this pair's `cap` slots
+    int cap, count;                                            // count: emitted in this push, written or not
+};
+
+__device__ __forceinline__ void emit(Detector& det, Events& out) {
+    if (out.count < out.cap) {
+        out.begin[out.count] = det.begin;
+        out.end[out.count] = det.end;
+        out.total[out.count] = det.total;
+        out.mean[out.count] = det.mean;
+    }
+    ++out.count;
+    ++det.events;
+    det.taken = det.end;
+    det.begin = -1;
+}
+
+// one frame of the detector: t is the absolute frame, (sum, first) its curve values
+__device__ __forceinline__ void detect(Detector& det, Events& out, int t, float sum, int first, float threshold,
+                                       int patience) {
+    if (det.begin >= 0 && t - (det.end - 1) > patience) emit(det, out);
+    if (first < 0 || first < det.taken) return;
+    const float value = sum / (float)(t - first + 1);
+    if (!(value >= threshold)) return;
+    if (det.begin >= 0) {
+        if (first < det.end) {                                 // the spans overlap: the better one stays, ties to the later
+            if (!(value >= det.mean)) return;
+        } else {
+            emit(det, out);
+        }
+    }
+    det.begin = first;
+    det.end = t + 1;
+    det.total = sum;
+    det.mean = value;
+}
+
+// search_strips for one push of T frames at position `base`: the strips come from `state_d`, `state_b` (64 * S words
+// each; the states at or above N run along as ever) and go back there; the lane of state N-1 runs the detector.  Wave-uniform control flow but for that lane's part.
+template <int S>
+__device__ __forceinline__ void search_stream_strips(const float4* __restrict__ src, int T, int N, int base,
+                                                     const int* __restrict__ sym, float* __restrict__ state_d,
+                                                     int* __restrict__ state_b, float* __restrict__ totals,
+                                                     int* __restrict__ begins, Detector& det, Events& out,
+                                                     float threshold, int patience, float4 (&stage)[2][CHUNK_VEC],
+                                                     int lane)
+{
+    int s[S], b[S]; float d[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        const int n = lane * S + k;
+        s[k] = n < N ? sym[n] : 0;                             // states at or above N run along on phoneme 0, unread
+        d[k] = state_d[n];
+        b[k] = state_b[n];
+    }
+    const int last = (N - 1) / S, place = (N - 1) % S;         // the lane of state N-1 and its place in the strip
+    float4 next[FETCH];
+    fetch(src, 0, T, lane, next);
+    stash(stage[0], lane, next);
+    __syncthreads();
+    int buf = 0;
+    for (int t0 = 0; t0 < T; t0 += CHUNK, buf ^= 1) {
+        fetch(src, t0 + CHUNK, T, lane, next);                 // in flight while this chunk is consumed
+        const float* e = reinterpret_cast<const float*>(stage[buf]);
+        const int count = min(CHUNK, T - t0);
+        float cur[S];                                          // frame t's emissions, read one frame ahead of their use
+        {
+            const float top = e[NP];
+#pragma unroll
+            for (int k = 0; k < S; ++k) cur[k] = e[s[k]] - top;
+        }
+        for (int u = 0; u < count; ++u) {
+            const int t = t0 + u;
+            const float* ahead = e + min(u + 1, CHUNK - 1) * PREP;       // (the last one re-reads a row: unused)
+            const float top = ahead[NP];
+            float coming[S];
+#pragma unroll
+            for (int k = 0; k < S; ++k) coming[k] = ahead[s[k]] - top;
+            // the state below the strip; below state 0 the origin: 0, beginning at this frame, at every frame
+            const float below = lane_up(d[S - 1], 0.f);
+            const int origin = lane_up_int(b[S - 1], base + t);
+#pragma unroll
+            for (int k = S - 1; k >= 0; --k) {                 // downwards: d[k - 1] and b[k - 1] are still frame t-1's
+                const float stay = d[k], from = k ? d[k - 1] : below;
+                const int source = k ? b[k - 1] : origin;
+                const bool advance = from > stay;
+                d[k] = cur[k] + (advance ? from : stay);       // -inf + finite = -inf: never NaN
+                b[k] = advance ? source : b[k];
+            }
+            if (lane == last) {
+                float end = d[0];
+                int first = b[0];
+#pragma unroll
+                for (int q = 1; q < S; ++q) {
+                    end = place == q ? d[q] : end;
+                    first = place == q ? b[q] : first;
+                }
+                if (totals) {
+                    totals[t] = end;
+                    begins[t] = first;
+                }
+                detect(det, out, base + t, end, first, threshold, patience);
+            }
+#pragma unroll
+            for (int k = 0; k < S; ++k) cur[k] = coming[k];
+        }
+        stash(stage[buf ^ 1], lane, next);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        state_d[lane * S + k] = d[k];
+        state_b[lane * S + k] = b[k];
+    }
+}
+
+// grid (queries, streams), 64 threads.  count = -1 for a pair that cannot be pushed, which touches nothing else; every
+// other pair gets the events of this push, sentinels behind them, and its state moved on by lengths[stream] frames.
+__global__ __launch_bounds__(64) void search_stream_programme(
+    const float* __restrict__ logp, int frames, const int* __restrict__ lengths, const int* __restrict__ phonemes,
+    int max_phonemes, const int* __restrict__ phoneme_lengths, const int* __restrict__ positions,
+    Detector* __restrict__ detectors, float* __restrict__ state_totals, int* __restrict__ state_begins,
+    float threshold, int patience, int cap, int* __restrict__ begin, int* __restrict__ end,
+    float* __restrict__ total, float* __restrict__ mean, int* __restrict__ count, float* __restrict__ curve_total,
+    int* __restrict__ curve_begin)
+{
+    __shared__ float4 stage[2][CHUNK_VEC];
+    const int query = blockIdx.x, item = blockIdx.y, lane = threadIdx.x;
+    const size_t pair = (size_t)item * gridDim.x + query;
+    const int T = lengths[item], N = phoneme_lengths[query], base = positions[item];
+    const int* sym = phonemes + (size_t)query * max_phonemes;
+    bool fine = T >= 0 && T <= frames && N >= 1 && N <= max_phonemes && base >= 0 && T <= INT32_MAX - base;
+    if (fine) {
+        bool bad = false;
+        for (int n = lane; n < N; n += 64) bad |= (unsigned)sym[n] >= (unsigned)NP;
+        fine = !__any(bad);
+    }
+    if (!fine) {                                               // (uniform)
+        if (lane == 0) count[pair] = -1;
+        return;
+    }
+    Events out{begin + pair * cap, end + pair * cap, total + pair * cap, mean + pair * cap, cap, 0};
+    const int last = N <= 64 ? N - 1 : (N - 1) >> 2;           // the lane of state N-1
+    if (T > 0) {                                               // (uniform) a stream with no frames sits out the step
+        const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
+        float* out_totals = curve_total ? curve_total + pair * frames : nullptr;
+        int* out_begins = curve_total ? curve_begin + pair * frames : nullptr;
+        float* own_d = state_totals + pair * stream_states(max_phonemes);
+        int* own_b = state_begins + pair * stream_states(max_phonemes);
+        Detector det = detectors[pair];                        // (every lane reads it; the lane of state N-1 uses it)
+        if (N <= 64)
+            search_stream_strips<1>(src, T, N, base, sym, own_d, own_b, out_totals, out_begins, det, out, threshold,
+                                    patience, stage, lane);
+        else
+            search_stream_strips<4>(src, T, N, base, sym, own_d, own_b, out_totals, out_begins, det, out, threshold,
+                                    patience, stage, lane);
+        if (lane == last) detectors[pair] = det;
+    }
+    const int events = __shfl(out.count, last);
+    if (lane == 0) count[pair] = events;
+    for (int h = min(events, cap) + lane; h < cap; h += 64) {
+        out.begin[h] = out.end[h] = -1;
+        out.total[h] = out.mean[h] = NAN;
+    }
+}
+
+// grid (ceil(streams / 64)), 64 threads: thread = stream.  The condition is the programme's own.
+__global__ __launch_bounds__(64) void search_stream_advance(int streams, int frames, const int* __restrict__ lengths,
+                                                             int* __restrict__ positions)
+{
+    const int item = blockIdx.x * 64 + threadIdx.x;
+    if (item >= streams) return;
+    const int T = lengths[item], base = positions[item];
+    if (T >= 0 && T <= frames && base >= 0 && T <= INT32_MAX - base) positions[item] = base + T;
+}
+
+// grid (ceil(streams * queries / 64)), 64 threads: thread = pair
+__global__ __launch_bounds__(64) void search_stream_flush(int streams, int queries, const int* __restrict__ which,
+                                                           Detector* __restrict__ detectors, int* __restrict__ begin,
+                                                           int* __restrict__ end, float* __restrict__ total,
+                                                           float* __restrict__ mean, int* __restrict__ count)
+{
+    const size_t pair = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (pair >= (size_t)streams * queries) return;
+    Detector det = detectors[pair];
+    const bool hit = (!which || which[pair / queries] != 0) && det.begin >= 0;
+    begin[pair] = hit ? det.begin : -1;
+    end[pair] = hit ? det.end : -1;
+    total[pair] = hit ? det.total : NAN;
+    mean[pair] = hit ? det.mean : NAN;
+    count[pair] = hit;
+    if (hit) {
+        ++det.events;
+        det.taken = det.end;
+        det.begin = -1;
+        detectors[pair] = det;
+    }
+}
+
+// grid (queries, streams), 64 threads
+__global__ __launch_bounds__(64) void search_stream_reset(int max_phonemes, const int* __restrict__ which,
+                                                           int* __restrict__ positions,
+                                                           Detector* __restrict__ detectors,
+                                                           float* __restrict__ state_totals,
+                                                           int* __restrict__ state_begins)
+{
+    const int query = blockIdx.x, item = blockIdx.y, lane = threadIdx.x;
+    if (which && which[item] == 0) return;                     // (uniform)
+    const size_t pair = (size_t)item * gridDim.x + query;
+    const int states = stream_states(max_phonemes);
+    for (int n = lane; n < states; n += 64) {
+        state_totals[pair * states + n] = -INFINITY;
+        state_begins[pair * states + n] = -1;
+    }
+    if (lane == 0) {
+        detectors[pair] = Detector{0, -1, 0, 0.f, 0.f, 0, {0, 0}};
+        if (query == 0) positions[item] = 0;
+    }
+}
+
+// the checks the three stream entries share: the state and its geometry
+int check_stream_state(const char* what, const void* state, int streams, int queries, int max_phonemes) {
+    if (!state || streams <= 0 || queries <= 0 || max_phonemes <= 0)
+        return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (streams > PPG_SEARCH_MAX_ITEMS)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d streams, at most %d per call", what, streams, PPG_SEARCH_MAX_ITEMS);
+    if (queries > PPG_SEARCH_MAX_QUERIES)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d queries, at most %d per call", what, queries,
+                                 PPG_SEARCH_MAX_QUERIES);
+    if (max_phonemes > PPG_SEARCH_MAX_PHONEMES)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d phonemes, at most %d", what, max_phonemes,
+                                 PPG_SEARCH_MAX_PHONEMES);
+    if (reinterpret_cast<uintptr_t>(state) % 16)
+        return ppg::fail_message(PPG_EINVAL, "%s: the state must be 16-byte aligned", what);
+    return PPG_OK;
+}
+
 int check_common(const char* what, const void* ppg, int frames, int items, const void* lengths) {
     if (!ppg || !lengths || items <= 0 || frames <= 0) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
     if (frames > PPG_ALIGN_MAX_FRAMES)
@@ -911,6 +1215,95 @@ int ppg_search(int device, const float* ppg, int frames, int items, const int32_
                        threshold, totals, begins, begin, end, total, mean, count, curve_total, curve_begin);
     const hipError_t he = hipGetLastError();
     return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "search: %s", hipGetErrorString(he));
+}
+
+size_t ppg_search_stream_state_bytes(int streams, int queries, int max_phonemes) {
+    if (streams <= 0 || streams > PPG_SEARCH_MAX_ITEMS || queries <= 0 || queries > PPG_SEARCH_MAX_QUERIES ||
+        max_phonemes <= 0 || max_phonemes > PPG_SEARCH_MAX_PHONEMES)
+        return 0;
+    return stream_layout(streams, queries, max_phonemes).bytes;
+}
+
+size_t ppg_search_stream_workspace_bytes(int streams, int frames, int queries) {
+    if (streams <= 0 || streams > PPG_SEARCH_MAX_ITEMS || frames <= 0 || frames > PPG_SEARCH_MAX_FRAMES ||
+        queries <= 0 || queries > PPG_SEARCH_MAX_QUERIES)
+        return 0;
+    return align256((size_t)streams * frames * PREP * sizeof(float));
+}
+
+int ppg_search_stream_reset(int device, void* state, int streams, int queries, int max_phonemes, const int32_t* which,
+                            void* stream) {
+    if (const int rc = check_stream_state("search_stream_reset", state, streams, queries, max_phonemes)) return rc;
+    if (hipSetDevice(device) != hipSuccess)
+        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    const StreamLayout w = stream_layout(streams, queries, max_phonemes);
+    char* st = static_cast<char*>(state);
+    hipLaunchKernelGGL(search_stream_reset, dim3(queries, streams), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       max_phonemes, which, reinterpret_cast<int*>(st + w.positions),
+                       reinterpret_cast<Detector*>(st + w.detectors), reinterpret_cast<float*>(st + w.totals),
+                       reinterpret_cast<int*>(st + w.begins));
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? PPG_OK
+                            : ppg::fail_message(PPG_EDEVICE, "search_stream_reset: %s", hipGetErrorString(he));
+}
+
+int ppg_search_stream_push(int device, void* state, const float* ppg, int frames, int streams, const int32_t* lengths,
+                           const int32_t* phonemes, int max_phonemes, int queries, const int32_t* phoneme_lengths,
+                           float threshold, int patience, int cap, int32_t* begin, int32_t* end, float* total,
+                           float* mean, int32_t* count, float* curve_total, int32_t* curve_begin, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    if (!ppg || !lengths || !phonemes || !phoneme_lengths || !begin || !end || !total || !mean || !count ||
+        !workspace || frames <= 0)
+        return ppg::fail_message(PPG_EINVAL, "search_stream_push: bad argument");
+    if (const int rc = check_stream_state("search_stream_push", state, streams, queries, max_phonemes)) return rc;
+    if (frames > PPG_SEARCH_MAX_FRAMES)
+        return ppg::fail_message(PPG_EINVAL, "search_stream_push: %d frames, at most %d", frames,
+                                 PPG_SEARCH_MAX_FRAMES);
+    if (threshold != threshold) return ppg::fail_message(PPG_EINVAL, "search_stream_push: the threshold is NaN");
+    if (patience < 0) return ppg::fail_message(PPG_EINVAL, "search_stream_push: patience = %d is negative", patience);
+    if (cap < 1) return ppg::fail_message(PPG_EINVAL, "search_stream_push: cap = %d, must be at least 1", cap);
+    if (!curve_total != !curve_begin)
+        return ppg::fail_message(PPG_EINVAL, "search_stream_push: curve_total and curve_begin go together");
+    const size_t need = align256((size_t)streams * frames * PREP * sizeof(float));
+    if (workspace_bytes < need)
+        return ppg::fail_message(PPG_EINVAL, "search_stream_push: workspace of %zu bytes, %zu needed", workspace_bytes,
+                                 need);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16)
+        return ppg::fail_message(PPG_EINVAL, "search_stream_push: workspace must be 16-byte aligned");
+    if (hipSetDevice(device) != hipSuccess)
+        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const StreamLayout w = stream_layout(streams, queries, max_phonemes);
+    char* st = static_cast<char*>(state);
+    int* positions = reinterpret_cast<int*>(st + w.positions);
+    float* logp = static_cast<float*>(workspace);
+    hipLaunchKernelGGL(align_prepare, dim3((frames + 63) / 64, streams), dim3(64), 0, s, ppg, frames, lengths, logp);
+    hipLaunchKernelGGL(search_stream_programme, dim3(queries, streams), dim3(64), 0, s, logp, frames, lengths, phonemes,
+                       max_phonemes, phoneme_lengths, positions, reinterpret_cast<Detector*>(st + w.detectors),
+                       reinterpret_cast<float*>(st + w.totals), reinterpret_cast<int*>(st + w.begins), threshold,
+                       patience, cap, begin, end, total, mean, count, curve_total, curve_begin);
+    hipLaunchKernelGGL(search_stream_advance, dim3((streams + 63) / 64), dim3(64), 0, s, streams, frames, lengths,
+                       positions);
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "search_stream_push: %s", hipGetErrorString(he));
+}
+
+int ppg_search_stream_flush(int device, void* state, int streams, int queries, int max_phonemes, const int32_t* which,
+                            int32_t* begin, int32_t* end, float* total, float* mean, int32_t* count, void* stream) {
+    if (!begin || !end || !total || !mean || !count)
+        return ppg::fail_message(PPG_EINVAL, "search_stream_flush: bad argument");
+    if (const int rc = check_stream_state("search_stream_flush", state, streams, queries, max_phonemes)) return rc;
+    if (hipSetDevice(device) != hipSuccess)
+        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    const StreamLayout w = stream_layout(streams, queries, max_phonemes);
+    const size_t pairs = (size_t)streams * queries;
+    hipLaunchKernelGGL(search_stream_flush, dim3((unsigned)((pairs + 63) / 64)), dim3(64), 0,
+                       static_cast<hipStream_t>(stream), streams, queries, which,
+                       reinterpret_cast<Detector*>(static_cast<char*>(state) + w.detectors), begin, end, total, mean,
+                       count);
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? PPG_OK
+                            : ppg::fail_message(PPG_EDEVICE, "search_stream_flush: %s", hipGetErrorString(he));
 }
 
 }  // extern "C"

@@ -168,6 +168,18 @@ SYMBOLS = {
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_size_t, ctypes.c_void_p]),
+    'ppg_search_stream_state_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_search_stream_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_search_stream_reset': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_search_stream_push': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'ppg_search_stream_flush': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_metrics_state_bytes': (ctypes.c_size_t, []),
     'ppg_metrics_reset': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_metrics_update': (ctypes.c_int, [
@@ -885,6 +897,72 @@ def search_items(ppg, lengths, table, counts, top=1, threshold=-math.inf, want_c
                     for out, part in zip(outputs, parts):
                         out[at:at + rows, low:low + columns].copy_(part)
     return begin, end, total, mean, count, curve
+
+
+def search_stream_state(device, streams, queries, most):
+    """The device block of a live search (ppg_search_stream_*), reset: `streams` streams x `queries` queries of at most
+    `most` phonemes.  uint8; its owner passes it to the three calls below with the same three numbers."""
+    size = library().ppg_search_stream_state_bytes(streams, queries, most)
+    if size == 0:
+        raise ValueError(f'a live search takes 1 to {SEARCH_MAX_ITEMS} streams, 1 to {SEARCH_MAX_QUERIES} queries and 1 to '
+                         f'{SEARCH_MAX_PHONEMES} phonemes, got {streams}, {queries} and {most}')
+    state = torch.empty((size,), dtype=torch.uint8, device=device)
+    search_stream_reset(state, streams, queries, most)
+    return state
+
+
+def search_stream_reset(state, streams, queries, most, which=None):
+    """ppg_search_stream_reset on the current stream: `which` is None (all) or a device int32 (streams,) of flags."""
+    with torch.cuda.device(state.device):
+        _check(library().ppg_search_stream_reset(
+            state.device.index, state.data_ptr(), streams, queries, most,
+            which.data_ptr() if which is not None else None, torch.cuda.current_stream().cuda_stream))
+
+
+def search_stream_push(state, ppg, lengths, table, counts, threshold, patience, cap, workspace, want_curve=False):
+    """ppg_search_stream_push on the current stream: ppg (streams, 40, frames) fp32, lengths (streams,) and counts
+    (queries,) int32, table (queries, most) int32, all contiguous on the state's device; workspace a uint8 tensor
+    there -> begin, end (streams, queries, cap) int32, total, mean fp32, count (streams, queries) int32 and the curve of
+    the pushed frames: None, or (curve_total fp32, curve_begin int32), each (streams, queries, frames) with -inf and
+    -1 at and past a stream's own length."""
+    device = state.device
+    streams, frames = ppg.shape[0], ppg.shape[2]
+    queries, most = table.shape
+    shape = (streams, queries, cap)
+    begin = torch.empty(shape, dtype=torch.int32, device=device)
+    end = torch.empty(shape, dtype=torch.int32, device=device)
+    total = torch.empty(shape, dtype=torch.float32, device=device)
+    mean = torch.empty(shape, dtype=torch.float32, device=device)
+    count = torch.empty((streams, queries), dtype=torch.int32, device=device)
+    curve = None
+    if want_curve:
+        curve = (torch.full((streams, queries, frames), -math.inf, dtype=torch.float32, device=device),
+                 torch.full((streams, queries, frames), -1, dtype=torch.int32, device=device))
+    with torch.cuda.device(device):
+        _check(library().ppg_search_stream_push(
+            device.index, state.data_ptr(), ppg.data_ptr(), frames, streams, lengths.data_ptr(), table.data_ptr(), most,
+            queries, counts.data_ptr(), threshold, patience, cap, begin.data_ptr(), end.data_ptr(), total.data_ptr(),
+            mean.data_ptr(), count.data_ptr(), curve[0].data_ptr() if curve else None,
+            curve[1].data_ptr() if curve else None, workspace.data_ptr(), workspace.numel(),
+            torch.cuda.current_stream().cuda_stream))
+    return begin, end, total, mean, count, curve
+
+
+def search_stream_flush(state, streams, queries, most, which=None):
+    """ppg_search_stream_flush on the current stream -> begin, end int32, total, mean fp32 (streams, queries, 1) and
+    count (streams, queries) int32: 1 where a hit was pending."""
+    device = state.device
+    begin = torch.empty((streams, queries, 1), dtype=torch.int32, device=device)
+    end = torch.empty((streams, queries, 1), dtype=torch.int32, device=device)
+    total = torch.empty((streams, queries, 1), dtype=torch.float32, device=device)
+    mean = torch.empty((streams, queries, 1), dtype=torch.float32, device=device)
+    count = torch.empty((streams, queries), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _check(library().ppg_search_stream_flush(
+            device.index, state.data_ptr(), streams, queries, most, which.data_ptr() if which is not None else None,
+            begin.data_ptr(), end.data_ptr(), total.data_ptr(), mean.data_ptr(), count.data_ptr(),
+            torch.cuda.current_stream().cuda_stream))
+    return begin, end, total, mean, count
 
 
 METRICS_FIXED_POINT = 2.0 ** 32        # the real-valued accumulators of PpgMetricsState count units of 2^-32
