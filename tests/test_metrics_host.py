@@ -42,13 +42,19 @@ def case_inputs(g, case):
     return logits, labels, lengths
 
 
-def restate(logits, labels, lengths=None, k=3, mix=None, class_weights=None, loss_weights=None):
-    """The seven accumulators in float64 torch (integers exact: comparisons of the fp32 logits themselves)."""
+def restate(logits, labels, lengths=None, k=3, mix=None, class_weights=None, loss_weights=None,
+            loss_clamp=2.0 ** 20):
+    """The seven accumulators in float64 torch (integers exact: comparisons of the fp32 logits themselves).
+    A frame's loss is brought into [0, loss_clamp] as the header states (None: left as it is); labels that are
+    neither -100 nor a class are counted in `invalid_labels` and ignored; `topk_by_k[j - 1]` is topk_correct at
+    k = j for every accepted k."""
     batch, classes, frames = logits.shape
     labels = labels.to(torch.int64).clone()
     if lengths is not None:
         labels[torch.arange(frames)[None, :] >= torch.as_tensor(lengths)[:, None]] = -100
     keep = labels.flatten() != -100
+    invalid = int((keep & ((labels.flatten() < 0) | (labels.flatten() >= classes))).sum())
+    keep = keep & (labels.flatten() >= 0) & (labels.flatten() < classes)
     rows = logits.float().transpose(1, 2).flatten(0, 1)[keep]
     target = labels.flatten()[keep]
     n = int(keep.sum())
@@ -59,6 +65,8 @@ def restate(logits, labels, lengths=None, k=3, mix=None, class_weights=None, los
     nll = -torch.log_softmax(rows.double(), dim=1).gather(1, target[:, None])[:, 0]
     if loss_weights is not None:
         nll = nll * loss_weights.double()[target]
+    if loss_clamp is not None:
+        nll = nll.clamp(0., loss_clamp)
     x, y = probs.clamp(1e-8, 1 - 1e-8).T, onehot.clamp(1e-8, 1 - 1e-8).T
     if mix is not None:
         x, y = mix.double() @ x, mix.double() @ y
@@ -69,7 +77,8 @@ def restate(logits, labels, lengths=None, k=3, mix=None, class_weights=None, los
     predicted = weighted.argmax(dim=1) if n else torch.zeros(0, dtype=torch.int64)
     return dict(
         count=n, true_positives=int(correct.sum()),
-        topk_correct=int((order[:, :k] == target[:, None]).sum()),
+        topk_correct=int((order[:, :k] == target[:, None]).sum()), invalid_labels=invalid,
+        topk_by_k=np.array([int((order[:, :j] == target[:, None]).sum()) for j in range(1, 9)]),
         class_total=torch.bincount(target[correct], minlength=classes).numpy(),
         class_count=torch.bincount(target, minlength=classes).numpy(),
         loss_sum=float(nll.sum()), jsd_sum=float(jsd.sum()),
