@@ -27,12 +27,19 @@
 //   D[t, n] = e[t, n] + best of  stay D[t-1, n],  advance D[t-1, n-1],  skip D[t-1, n-2] if opt[n-1]
 //   strict comparisons in that order: stay beats advance beats skip on ties.  State -1 holds 0 before frame 0.
 //   The end is state N-1, or N-2 if opt[N-1] and D[T-1, N-2] > D[T-1, N-1].
-// align_prepare is shared; three kernels of their own beside the ones above, which stay as they are:
+// align_prepare is shared; three kernels beside the ones above:
 //   align_programme_optional   the same wave, strips and staging; a second value from below the strip (a second
 //                              cross-lane move), the states' skip permissions as a bit mask in one register, and two
 //                              direction planes (advance, skip) of the 16-bit-per-lane format.
 //   align_traceback_optional   both planes through LDS 64 frames at a time; a skip writes two starts.
 //   align_score_optional       align_score for transcripts that may be longer than the utterance.
+//
+// What the kernels share stands once: WALK_FRAMES is the frame loop (staging, double buffering, the gather one frame
+// ahead, the barriers) of the four programmes, each of which hands it its recurrence.  `search_strips` is
+// the one body of both searches, `traceback` of both trace-backs (one or two bit planes), `score_phoneme` of both
+// scores, `refused` their test of an utterance the programme refused, `symbols_fine` the phoneme range check.  The
+// __global__ entries keep their names and are thin where a body is shared.  The host entries share their rungs
+// (check_*, select_device, launched) at the end of the file.
 #include "../../include/ppgs_amd.h"
 
 #include <hip/hip_runtime.h>
@@ -57,31 +64,24 @@ constexpr int ROW_VEC = ROW * 2 / 16;         // a direction row as 16-byte piec
 constexpr int WALK = 64;                      // frames per LDS refill of the trace-back
 
 struct Layout {
-    size_t logp, dirs, bytes;                 // byte offsets into the workspace
-};
-
-struct OptionalLayout {
-    size_t logp, dirs, skips, ends, bytes;    // as Layout, then the skip plane and the end state of every utterance
-};
+    size_t logp, dirs, skips, ends, bytes;    // byte offsets into the workspace; with optional phonemes also the skip
+};                                            // plane and the end state of every utterance
 
 inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 
-inline Layout layout(int items, int frames) {
-    Layout w{};
-    size_t at = 0;
-    w.logp = at; at = align256(at + (size_t)items * frames * PREP * sizeof(float));
-    w.dirs = at; at = align256(at + (size_t)items * frames * ROW * sizeof(uint16_t));
-    w.bytes = at;
-    return w;
-}
+// the prepared frames of a call: the first block of every workspace, and the whole workspace of a stream's push
+inline size_t prepared_bytes(int items, int frames) { return align256((size_t)items * frames * PREP * sizeof(float)); }
 
-inline OptionalLayout optional_layout(int items, int frames) {
-    OptionalLayout w{};
+inline Layout layout(int items, int frames, bool optional) {
+    Layout w{};
+    const size_t plane = (size_t)items * frames * ROW * sizeof(uint16_t);
     size_t at = 0;
-    w.logp = at; at = align256(at + (size_t)items * frames * PREP * sizeof(float));
-    w.dirs = at; at = align256(at + (size_t)items * frames * ROW * sizeof(uint16_t));
-    w.skips = at; at = align256(at + (size_t)items * frames * ROW * sizeof(uint16_t));
-    w.ends = at; at = align256(at + (size_t)items * sizeof(int));
+    w.logp = at; at += prepared_bytes(items, frames);
+    w.dirs = at; at = align256(at + plane);
+    if (optional) {
+        w.skips = at; at = align256(at + plane);
+        w.ends = at; at = align256(at + (size_t)items * sizeof(int));
+    }
     w.bytes = at;
     return w;
 }
@@ -117,9 +117,21 @@ __global__ __launch_bounds__(64) void align_prepare(const float* __restrict__ pp
 }
 
 // lane l <- lane l - 1; lane 0 <- first.  Call it from wave-uniform control flow only.
+__device__ __forceinline__ int lane_up(int v, int first) {
+    return __builtin_amdgcn_update_dpp(first, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+}
 __device__ __forceinline__ float lane_up(float v, float first) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(first), __float_as_int(v), 0x138 /* wave_shr:1 */,
-                                                      0xf, 0xf, false));
+    return __int_as_float(lane_up(__float_as_int(v), __float_as_int(first)));
+}
+
+// the phoneme range check: whether `symbol` is none of the 40
+__device__ __forceinline__ bool bad_symbol(int symbol) { return (unsigned)symbol >= (unsigned)NP; }
+
+// whether every phoneme of sym[0 .. N-1] is one of the 40: the same answer in every lane (call it uniformly)
+__device__ __forceinline__ bool symbols_fine(const int* __restrict__ sym, int N, int lane) {
+    bool bad = false;
+    for (int n = lane; n < N; n += 64) bad |= bad_symbol(sym[n]);
+    return !__any(bad);
 }
 
 // the prepared frames t0 .. t0 + CHUNK - 1 of one utterance, those below T only, one 16-byte piece per lane and u
@@ -140,6 +152,44 @@ __device__ __forceinline__ void stash(float4* __restrict__ stage, int lane, cons
     }
 }
 
+// The frame walk of every programme below, once: BODY runs once per frame `t` = 0 .. T-1 in order with `cur`, the
+// emissions of the lane's strip (RELATIVE: less the frame's maximum, float NP of the frame: a broadcast).  The prepared
+// frames come through LDS CHUNK at a time, double-buffered: the next chunk's loads are in flight while the current one
+// is consumed, and the gather itself runs one frame ahead of its use.  It reads `src`, `T`, `s`, `stage` and `lane` of
+// the programme it stands in, holds the barriers, so it stands in wave-uniform control flow only; BODY may diverge.
+// A macro and not a function taking BODY as a lambda: as a function the same statements built to other schedules and
+// other places in the instruction stream (align_programme 6 %, search_programme 7 - 9 % slower, the programme with
+// optional phonemes 144 VGPRs for 119), as a macro the compiler sees the written-out loop.
+#define WALK_FRAMES(S, RELATIVE, t, cur, ...)                                                                          \
+    {                                                                                                                  \
+        float4 next[FETCH];                                                                                            \
+        fetch(src, 0, T, lane, next);                                                                                  \
+        stash(stage[0], lane, next);                                                                                   \
+        __syncthreads();                                                                                               \
+        int buf = 0;                                                                                                   \
+        for (int t0 = 0; t0 < T; t0 += CHUNK, buf ^= 1) {                                                              \
+            fetch(src, t0 + CHUNK, T, lane, next);             /* in flight while this chunk is consumed */            \
+            const float* e = reinterpret_cast<const float*>(stage[buf]);                                               \
+            const int count = min(CHUNK, T - t0);                                                                      \
+            float cur[S];                                      /* frame t's, read one frame ahead of their use */      \
+            {                                                                                                          \
+                const float top = RELATIVE ? e[NP] : 0.f;                                                              \
+                _Pragma("unroll") for (int k = 0; k < S; ++k) cur[k] = RELATIVE ? e[s[k]] - top : e[s[k]];             \
+            }                                                                                                          \
+            for (int u = 0; u < count; ++u) {                                                                          \
+                const int t = t0 + u;                                                                                  \
+                const float* ahead = e + min(u + 1, CHUNK - 1) * PREP;   /* (the last one re-reads a row: unused) */   \
+                const float top = RELATIVE ? ahead[NP] : 0.f;                                                          \
+                float coming[S];                                                                                       \
+                _Pragma("unroll") for (int k = 0; k < S; ++k) coming[k] = RELATIVE ? ahead[s[k]] - top : ahead[s[k]];  \
+                __VA_ARGS__                                                                                            \
+                _Pragma("unroll") for (int k = 0; k < S; ++k) cur[k] = coming[k];                                      \
+            }                                                                                                          \
+            stash(stage[buf ^ 1], lane, next);                 /* its readers passed the barrier below */              \
+            __syncthreads();                                                                                           \
+        }                                                                                                              \
+    }
+
 // The programme of one utterance with S states per lane.  Everything here is wave-uniform control flow.
 template <int S>
 __device__ __forceinline__ float programme(const float4* __restrict__ src, int T, int N, const int* __restrict__ sym,
@@ -152,41 +202,17 @@ __device__ __forceinline__ float programme(const float4* __restrict__ src, int T
         s[k] = n < N ? sym[n] : 0;                             // states at or above N run along on phoneme 0, unread
         d[k] = -INFINITY;
     }
-    float4 next[FETCH];
-    fetch(src, 0, T, lane, next);
-    stash(stage[0], lane, next);
-    __syncthreads();
-    int buf = 0;
-    for (int t0 = 0; t0 < T; t0 += CHUNK, buf ^= 1) {
-        fetch(src, t0 + CHUNK, T, lane, next);                 // in flight while this chunk is consumed
-        const float* e = reinterpret_cast<const float*>(stage[buf]);
-        const int count = min(CHUNK, T - t0);
-        float cur[S];                                          // frame t's emissions, read one frame ahead of their use
-#pragma unroll
-        for (int k = 0; k < S; ++k) cur[k] = e[s[k]];
-        for (int u = 0; u < count; ++u) {
-            const int t = t0 + u;
-            const float* ahead = e + min(u + 1, CHUNK - 1) * PREP;       // (the last one re-reads a row: unused)
-            float coming[S];
-#pragma unroll
-            for (int k = 0; k < S; ++k) coming[k] = ahead[s[k]];
-            // the state below the strip; for the very first cell the virtual origin D[-1, -1] = 0, so D[0, 0] = e + 0
-            const float below = lane_up(d[S - 1], t == 0 ? 0.f : -INFINITY);
-            uint32_t bits = 0;
-#pragma unroll
-            for (int k = S - 1; k >= 0; --k) {                 // downwards: d[k - 1] is still frame t-1's
-                const float stay = d[k], from = k ? d[k - 1] : below;
-                const bool advance = from > stay;
-                d[k] = cur[k] + (advance ? from : stay);       // -inf + finite = -inf: never NaN
-                bits |= (uint32_t)advance << k;
-            }
-            dirs[(size_t)t * ROW + lane] = (uint16_t)bits;
-#pragma unroll
-            for (int k = 0; k < S; ++k) cur[k] = coming[k];
+    WALK_FRAMES(S, false, t, cur,
+        // the state below the strip; for the very first cell the virtual origin D[-1, -1] = 0, so D[0, 0] = e + 0
+        const float below = lane_up(d[S - 1], t == 0 ? 0.f : -INFINITY);
+        uint32_t bits = 0;
+        _Pragma("unroll") for (int k = S - 1; k >= 0; --k) {   // downwards: d[k - 1] is still frame t-1's
+            const float stay = d[k], from = k ? d[k - 1] : below;
+            const bool advance = from > stay;
+            d[k] = cur[k] + (advance ? from : stay);           // -inf + finite = -inf: never NaN
+            bits |= (uint32_t)advance << k;
         }
-        stash(stage[buf ^ 1], lane, next);
-        __syncthreads();
-    }
+        dirs[(size_t)t * ROW + lane] = (uint16_t)bits;)
     const int k = (N - 1) % S;
     float last = d[0];
 #pragma unroll
@@ -206,11 +232,7 @@ __global__ __launch_bounds__(64) void align_programme(const float* __restrict__ 
     const int T = lengths[item], N = phoneme_lengths[item];
     const int* sym = phonemes + (size_t)item * max_phonemes;
     bool fine = plausible(T, N, frames, max_phonemes);
-    if (fine) {
-        bool bad = false;
-        for (int n = lane; n < N; n += 64) bad |= (unsigned)sym[n] >= (unsigned)NP;
-        fine = !__any(bad);
-    }
+    if (fine) fine = symbols_fine(sym, N, lane);
     if (!fine) {                                               // (uniform)
         if (lane == 0) total[item] = NAN;
         return;
@@ -225,61 +247,94 @@ __global__ __launch_bounds__(64) void align_programme(const float* __restrict__ 
     if (lane == (N - 1) >> shift) total[item] = last;
 }
 
-// grid (items), 64 threads.  An utterance whose total is NaN was refused by the programme: starts stay untouched.
-__global__ __launch_bounds__(64) void align_traceback(const uint16_t* __restrict__ dirs, int frames,
-                                                       const int* __restrict__ lengths, int max_phonemes,
-                                                       const int* __restrict__ phoneme_lengths,
-                                                       const float* __restrict__ total, int* __restrict__ starts)
+// What the kernels after a programme ask first: an utterance whose total is NaN was refused by it and stays untouched.
+// The plain alignment repeats the programme's test of the lengths; with optional phonemes (N may exceed T) that NaN
+// alone says it, so the lengths of a refused utterance are loaded and never used.
+template <bool Optional>
+__device__ __forceinline__ bool refused(int T, int N, int frames, int max_phonemes, const float* __restrict__ total) {
+    return (!Optional && !plausible(T, N, frames, max_phonemes)) || *total != *total;
+}
+
+// The trace-back of one utterance over PLANES bit planes of directions: the advance plane and, with Skips, the skip
+// plane, whose set bit overrides it; the walk begins in state `end`.  Wave-uniform control flow.
+template <bool Skips, int PLANES>
+__device__ __forceinline__ void traceback(const uint4* const (&src)[PLANES], int T, int N, int end,
+                                          int* __restrict__ out, uint4 (&rows)[PLANES][WALK * ROW_VEC], int lane)
 {
-    __shared__ uint4 rows[WALK * ROW_VEC];
-    const int item = blockIdx.x, lane = threadIdx.x;
-    const int T = lengths[item], N = phoneme_lengths[item];
-    if (!plausible(T, N, frames, max_phonemes) || total[item] != total[item]) return;
+    static_assert(PLANES == (Skips ? 2 : 1), "one plane, or two with skips");
     const int shift = strip_shift(N), mask = (1 << shift) - 1;
-    const uint4* src = reinterpret_cast<const uint4*>(dirs + (size_t)item * frames * ROW);
-    int* out = starts + (size_t)item * (max_phonemes + 1);
-    uint4 next[ROW_VEC];
+    uint4 next[PLANES][ROW_VEC];
     auto load = [&](int c) {                                   // rows of frames c * WALK ..., those below T only
         const int pieces = min(WALK, T - c * WALK) * ROW_VEC;
 #pragma unroll
         for (int u = 0; u < ROW_VEC; ++u) {
             const int idx = u * 64 + lane;
-            next[u] = idx < pieces ? src[(size_t)c * WALK * ROW_VEC + idx] : make_uint4(0, 0, 0, 0);
+#pragma unroll
+            for (int p = 0; p < PLANES; ++p)
+                next[p][u] = idx < pieces ? src[p][(size_t)c * WALK * ROW_VEC + idx] : make_uint4(0, 0, 0, 0);
         }
     };
-    int n = N - 1;
+    int n = end;
     int c = (T - 1) / WALK;
     load(c);
     for (; c >= 0; --c) {
         __syncthreads();                                       // the walk over the previous refill is over
 #pragma unroll
-        for (int u = 0; u < ROW_VEC; ++u) rows[u * 64 + lane] = next[u];
+        for (int u = 0; u < ROW_VEC; ++u) {
+#pragma unroll
+            for (int p = 0; p < PLANES; ++p) rows[p][u * 64 + lane] = next[p][u];
+        }
         __syncthreads();
         if (c > 0) load(c - 1);
-        const uint16_t* row = reinterpret_cast<const uint16_t*>(rows);
+        const uint16_t* row = reinterpret_cast<const uint16_t*>(rows[0]);
+        const uint16_t* row_skips = reinterpret_cast<const uint16_t*>(rows[PLANES - 1]);
         const int low = max(c * WALK, 1);
         for (int t = min(T - 1, c * WALK + WALK - 1); t >= low; --t) {
-            const uint32_t word = row[(t & (WALK - 1)) * ROW + (n >> shift)];      // the same address in every lane
-            if (n > 0 && ((word >> (n & mask)) & 1)) {
+            const int at = (t & (WALK - 1)) * ROW + (n >> shift), bit = n & mask;  // the same address in every lane
+            const uint32_t word = row[at], jump = Skips ? row_skips[at] : 0;
+            if (Skips && n > 1 && ((jump >> bit) & 1)) {       // over the optional phoneme n - 1: it gets no frame
+                if (lane == 0) { out[n] = t; out[n - 1] = t; }
+                n -= 2;
+            } else if (n > 0 && ((word >> bit) & 1)) {
                 if (lane == 0) out[n] = t;
                 --n;
             }
         }
     }
-    if (lane == 0) { out[0] = 0; out[N] = T; }
+    if (lane == 0) {
+        if (Skips && n == 1) out[1] = 0;                       // the path began in state 1: phoneme 0 was left out
+        out[0] = 0;
+        if (Skips && end == N - 2) out[N - 1] = T;             // ... ended in state N - 2: phoneme N - 1 was left out
+        out[N] = T;
+    }
 }
 
-// grid (ceil(max_phonemes / 64), items), 64 threads: thread = phoneme
-__global__ __launch_bounds__(64) void align_score(const float* __restrict__ logp, int frames,
-                                                   const int* __restrict__ lengths,
-                                                   const int* __restrict__ phonemes, int max_phonemes,
-                                                   const int* __restrict__ phoneme_lengths,
-                                                   const float* __restrict__ total, const int* __restrict__ starts,
-                                                   float* __restrict__ score, float* __restrict__ gop)
+// grid (items), 64 threads
+__global__ __launch_bounds__(64) void align_traceback(const uint16_t* __restrict__ dirs, int frames,
+                                                       const int* __restrict__ lengths, int max_phonemes,
+                                                       const int* __restrict__ phoneme_lengths,
+                                                       const float* __restrict__ total, int* __restrict__ starts)
+{
+    __shared__ uint4 rows[1][WALK * ROW_VEC];
+    const int item = blockIdx.x;
+    const int T = lengths[item], N = phoneme_lengths[item];
+    if (refused<false>(T, N, frames, max_phonemes, total + item)) return;
+    const uint4* const src[1] = {reinterpret_cast<const uint4*>(dirs + (size_t)item * frames * ROW)};
+    traceback<false>(src, T, N, N - 1, starts + (size_t)item * (max_phonemes + 1), rows, threadIdx.x);
+}
+
+// The scores of one phoneme, thread = phoneme of grid (ceil(max_phonemes / 64), items), 64 threads.  Optional: the
+// transcript may be longer than its utterance, and a phoneme that was left out has an empty segment: 0 / 0 = NaN.
+template <bool Optional>
+__device__ __forceinline__ void score_phoneme(const float* __restrict__ logp, int frames,
+                                              const int* __restrict__ lengths, const int* __restrict__ phonemes,
+                                              int max_phonemes, const int* __restrict__ phoneme_lengths,
+                                              const float* __restrict__ total, const int* __restrict__ starts,
+                                              float* __restrict__ score, float* __restrict__ gop)
 {
     const int item = blockIdx.y, n = blockIdx.x * 64 + threadIdx.x;
     const int T = lengths[item], N = phoneme_lengths[item];
-    if (!plausible(T, N, frames, max_phonemes) || total[item] != total[item] || n >= N) return;
+    if (refused<Optional>(T, N, frames, max_phonemes, total + item) || n >= N) return;
     const int* bounds = starts + (size_t)item * (max_phonemes + 1) + n;
     const int first = max(bounds[0], 0), end = min(bounds[1], T);
     const float* row = logp + (size_t)item * frames * PREP + phonemes[(size_t)item * max_phonemes + n];
@@ -293,6 +348,17 @@ __global__ __launch_bounds__(64) void align_score(const float* __restrict__ logp
     const float count = (float)(end - first);
     score[(size_t)item * max_phonemes + n] = sum / count;
     if (gop) gop[(size_t)item * max_phonemes + n] = below / count;
+}
+
+// grid (ceil(max_phonemes / 64), items), 64 threads
+__global__ __launch_bounds__(64) void align_score(const float* __restrict__ logp, int frames,
+                                                   const int* __restrict__ lengths,
+                                                   const int* __restrict__ phonemes, int max_phonemes,
+                                                   const int* __restrict__ phoneme_lengths,
+                                                   const float* __restrict__ total, const int* __restrict__ starts,
+                                                   float* __restrict__ score, float* __restrict__ gop)
+{
+    score_phoneme<false>(logp, frames, lengths, phonemes, max_phonemes, phoneme_lengths, total, starts, score, gop);
 }
 
 // grid (items), 64 threads: lane = frame of the current 64
@@ -322,7 +388,7 @@ __global__ __launch_bounds__(64) void decode_runs(const float* __restrict__ ppg,
                 if (v > best) { best = v; label = p; }         // the lowest index on ties
             }
         }
-        const int before = __builtin_amdgcn_update_dpp(carry, label, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+        const int before = lane_up(label, carry);
         const bool opens = t < T && label != before;
         const unsigned long long mask = __ballot(opens);
         if (opens) {
@@ -355,48 +421,24 @@ __device__ __forceinline__ int programme_optional(const float4* __restrict__ src
         may |= (uint32_t)(n >= 1 && n < N && opt[n - 1] != 0) << k;
         d[k] = -INFINITY;
     }
-    float4 next[FETCH];
-    fetch(src, 0, T, lane, next);
-    stash(stage[0], lane, next);
-    __syncthreads();
-    int buf = 0;
-    for (int t0 = 0; t0 < T; t0 += CHUNK, buf ^= 1) {
-        fetch(src, t0 + CHUNK, T, lane, next);                 // in flight while this chunk is consumed
-        const float* e = reinterpret_cast<const float*>(stage[buf]);
-        const int count = min(CHUNK, T - t0);
-        float cur[S];                                          // frame t's emissions, read one frame ahead of their use
-#pragma unroll
-        for (int k = 0; k < S; ++k) cur[k] = e[s[k]];
-        for (int u = 0; u < count; ++u) {
-            const int t = t0 + u;
-            const float* ahead = e + min(u + 1, CHUNK - 1) * PREP;       // (the last one re-reads a row: unused)
-            float coming[S];
-#pragma unroll
-            for (int k = 0; k < S; ++k) coming[k] = ahead[s[k]];
-            // the two states below the strip.  The virtual origin, state -1, holds 0 before frame 0 and -inf after it:
-            // it is `below` of state 0 and, where phoneme 0 is optional, `under` of state 1.
-            const float below = lane_up(d[S - 1], t == 0 ? 0.f : -INFINITY);
-            const float under = S == 1 ? lane_up(below, -INFINITY) : lane_up(d[S > 1 ? S - 2 : 0], -INFINITY);
-            uint32_t bits = 0, jumps = 0;
-#pragma unroll
-            for (int k = S - 1; k >= 0; --k) {                 // downwards: d[k - 1] and d[k - 2] are still frame t-1's
-                const float stay = d[k], from = k ? d[k - 1] : below;
-                const float over = k >= 2 ? d[k >= 2 ? k - 2 : 0] : k == 1 ? below : under;
-                const bool advance = from > stay;
-                const float best = advance ? from : stay;
-                const bool skip = ((may >> k) & 1) && over > best;
-                d[k] = cur[k] + (skip ? over : best);          // -inf + finite = -inf: never NaN
-                bits |= (uint32_t)advance << k;                // (a set skip bit overrides it in the trace-back)
-                jumps |= (uint32_t)skip << k;
-            }
-            dirs[(size_t)t * ROW + lane] = (uint16_t)bits;
-            skips[(size_t)t * ROW + lane] = (uint16_t)jumps;
-#pragma unroll
-            for (int k = 0; k < S; ++k) cur[k] = coming[k];
+    WALK_FRAMES(S, false, t, cur,
+        // the two states below the strip.  The virtual origin, state -1, holds 0 before frame 0 and -inf after it:
+        // it is `below` of state 0 and, where phoneme 0 is optional, `under` of state 1.
+        const float below = lane_up(d[S - 1], t == 0 ? 0.f : -INFINITY);
+        const float under = S == 1 ? lane_up(below, -INFINITY) : lane_up(d[S > 1 ? S - 2 : 0], -INFINITY);
+        uint32_t bits = 0; uint32_t jumps = 0;
+        _Pragma("unroll") for (int k = S - 1; k >= 0; --k) {   // downwards: d[k - 1] and d[k - 2] are still frame t-1's
+            const float stay = d[k]; const float from = k ? d[k - 1] : below;
+            const float over = k >= 2 ? d[k >= 2 ? k - 2 : 0] : k == 1 ? below : under;
+            const bool advance = from > stay;
+            const float best = advance ? from : stay;
+            const bool skip = ((may >> k) & 1) && over > best;
+            d[k] = cur[k] + (skip ? over : best);              // -inf + finite = -inf: never NaN
+            bits |= (uint32_t)advance << k;                    // (a set skip bit overrides it in the trace-back)
+            jumps |= (uint32_t)skip << k;
         }
-        stash(stage[buf ^ 1], lane, next);
-        __syncthreads();
-    }
+        dirs[(size_t)t * ROW + lane] = (uint16_t)bits;
+        skips[(size_t)t * ROW + lane] = (uint16_t)jumps;)
     const int k = (N - 1) % S, j = (N + S - 2) % S;            // the last state's place in its strip; the one below it
     float last = d[0], before = d[0];
 #pragma unroll
@@ -427,7 +469,7 @@ __global__ __launch_bounds__(64) void align_programme_optional(const float* __re
     const int* sym = phonemes + (size_t)item * max_phonemes;
     const int* opt = optional + (size_t)item * max_phonemes;
     bool fine = T >= 1 && T <= frames && N >= 1 && N <= max_phonemes;
-    if (fine) {
+    if (fine) {                                                // one pass over the transcript: phonemes and flags
         bool bad = false;
         int mandatory = 0;
         for (int base = 0; base < N; base += 64) {             // (uniform)
@@ -435,7 +477,7 @@ __global__ __launch_bounds__(64) void align_programme_optional(const float* __re
             bool needed = false;
             if (n < N) {
                 needed = opt[n] == 0;
-                bad |= (unsigned)sym[n] >= (unsigned)NP;
+                bad |= bad_symbol(sym[n]);
                 bad |= !needed && n + 1 < N && opt[n + 1] != 0;            // two optional phonemes in a row
             }
             mandatory += __popcll(__ballot(needed));
@@ -458,8 +500,7 @@ __global__ __launch_bounds__(64) void align_programme_optional(const float* __re
     if (lane == 0) { total[item] = sum; ends[item] = end; }
 }
 
-// grid (items), 64 threads.  An utterance whose total is NaN was refused by the programme, which checked its lengths:
-// starts stay untouched.  Every other utterance has its end state in `ends`.
+// grid (items), 64 threads.  Every utterance the programme did not refuse has its end state in `ends`.
 __global__ __launch_bounds__(64) void align_traceback_optional(const uint16_t* __restrict__ dirs,
                                                                 const uint16_t* __restrict__ skips, int frames,
                                                                 const int* __restrict__ lengths, int max_phonemes,
@@ -468,63 +509,16 @@ __global__ __launch_bounds__(64) void align_traceback_optional(const uint16_t* _
                                                                 const int* __restrict__ ends, int* __restrict__ starts)
 {
     __shared__ uint4 rows[2][WALK * ROW_VEC];
-    const int item = blockIdx.x, lane = threadIdx.x;
-    if (total[item] != total[item]) return;
+    const int item = blockIdx.x;
     const int T = lengths[item], N = phoneme_lengths[item];
-    const int shift = strip_shift(N), mask = (1 << shift) - 1;
-    const uint4* src = reinterpret_cast<const uint4*>(dirs + (size_t)item * frames * ROW);
-    const uint4* src_skips = reinterpret_cast<const uint4*>(skips + (size_t)item * frames * ROW);
-    int* out = starts + (size_t)item * (max_phonemes + 1);
-    uint4 next[2][ROW_VEC];
-    auto load = [&](int c) {                                   // rows of frames c * WALK ..., those below T only
-        const int pieces = min(WALK, T - c * WALK) * ROW_VEC;
-#pragma unroll
-        for (int u = 0; u < ROW_VEC; ++u) {
-            const int idx = u * 64 + lane;
-            const bool in = idx < pieces;
-            next[0][u] = in ? src[(size_t)c * WALK * ROW_VEC + idx] : make_uint4(0, 0, 0, 0);
-            next[1][u] = in ? src_skips[(size_t)c * WALK * ROW_VEC + idx] : make_uint4(0, 0, 0, 0);
-        }
-    };
-    const int end = min(max(ends[item], 0), N - 1);
-    int n = end;
-    int c = (T - 1) / WALK;
-    load(c);
-    for (; c >= 0; --c) {
-        __syncthreads();                                       // the walk over the previous refill is over
-#pragma unroll
-        for (int u = 0; u < ROW_VEC; ++u) {
-            rows[0][u * 64 + lane] = next[0][u];
-            rows[1][u * 64 + lane] = next[1][u];
-        }
-        __syncthreads();
-        if (c > 0) load(c - 1);
-        const uint16_t* row = reinterpret_cast<const uint16_t*>(rows[0]);
-        const uint16_t* row_skips = reinterpret_cast<const uint16_t*>(rows[1]);
-        const int low = max(c * WALK, 1);
-        for (int t = min(T - 1, c * WALK + WALK - 1); t >= low; --t) {
-            const int at = (t & (WALK - 1)) * ROW + (n >> shift), bit = n & mask;  // the same address in every lane
-            const uint32_t word = row[at], jump = row_skips[at];
-            if (n > 1 && ((jump >> bit) & 1)) {                // over the optional phoneme n - 1: it gets no frame
-                if (lane == 0) { out[n] = t; out[n - 1] = t; }
-                n -= 2;
-            } else if (n > 0 && ((word >> bit) & 1)) {
-                if (lane == 0) out[n] = t;
-                --n;
-            }
-        }
-    }
-    if (lane == 0) {
-        if (n == 1) out[1] = 0;                                // the path began in state 1: phoneme 0 was left out
-        out[0] = 0;
-        if (end == N - 2) out[N - 1] = T;                      // ... ended in state N - 2: phoneme N - 1 was left out
-        out[N] = T;
-    }
+    if (refused<true>(T, N, frames, max_phonemes, total + item)) return;
+    const uint4* const src[2] = {reinterpret_cast<const uint4*>(dirs + (size_t)item * frames * ROW),
+                                 reinterpret_cast<const uint4*>(skips + (size_t)item * frames * ROW)};
+    traceback<true>(src, T, N, min(max(ends[item], 0), N - 1), starts + (size_t)item * (max_phonemes + 1), rows,
+                    threadIdx.x);
 }
 
-// grid (ceil(max_phonemes / 64), items), 64 threads: thread = phoneme.  align_score, statement for statement, without
-// its refusal of N > T: the programme has checked the lengths of every utterance whose total is not NaN.  A phoneme
-// that was left out has an empty segment: 0 / 0 = NaN.
+// grid (ceil(max_phonemes / 64), items), 64 threads
 __global__ __launch_bounds__(64) void align_score_optional(const float* __restrict__ logp, int frames,
                                                             const int* __restrict__ lengths,
                                                             const int* __restrict__ phonemes, int max_phonemes,
@@ -533,23 +527,7 @@ __global__ __launch_bounds__(64) void align_score_optional(const float* __restri
                                                             const int* __restrict__ starts,
                                                             float* __restrict__ score, float* __restrict__ gop)
 {
-    const int item = blockIdx.y, n = blockIdx.x * 64 + threadIdx.x;
-    if (total[item] != total[item]) return;
-    const int T = lengths[item], N = phoneme_lengths[item];
-    if (n >= N) return;
-    const int* bounds = starts + (size_t)item * (max_phonemes + 1) + n;
-    const int first = max(bounds[0], 0), end = min(bounds[1], T);
-    const float* row = logp + (size_t)item * frames * PREP + phonemes[(size_t)item * max_phonemes + n];
-    const float* top = logp + (size_t)item * frames * PREP + NP;
-    float sum = 0.f, below = 0.f;
-    for (int t = first; t < end; ++t) {
-        const float e = row[(size_t)t * PREP];
-        sum += e;
-        if (gop) below += e - top[(size_t)t * PREP];           // exactly 0 where the target is the frame's maximum
-    }
-    const float count = (float)(end - first);
-    score[(size_t)item * max_phonemes + n] = sum / count;
-    if (gop) gop[(size_t)item * max_phonemes + n] = below / count;
+    score_phoneme<true>(logp, frames, lengths, phonemes, max_phonemes, phoneme_lengths, total, starts, score, gop);
 }
 
 // ---- phrase search (ppg_search) ----
@@ -578,22 +556,79 @@ inline SearchLayout search_layout(int items, int frames, int queries) {
     SearchLayout w{};
     const size_t curve = (size_t)items * queries * frames * sizeof(float);
     size_t at = 0;
-    w.logp = at; at = align256(at + (size_t)items * frames * PREP * sizeof(float));
+    w.logp = at; at += prepared_bytes(items, frames);
     w.totals = at; at = align256(at + curve);
     w.begins = at; at = align256(at + curve);
     w.bytes = at;
     return w;
 }
 
-// lane_up for integers
-__device__ __forceinline__ int lane_up_int(int v, int first) {
-    return __builtin_amdgcn_update_dpp(first, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+// The online detector of the live search (its rule stands with the live search below): the search body
+// right after it runs it on every frame of a push.
+constexpr int DETECTOR = 8;                   // words of a pair's detector
+struct Detector {
+    int taken, begin, end;                    // begin = -1: nothing is pending
+    float total, mean;
+    int events;                               // hits emitted since the reset
+    int reserved[2];
+};
+static_assert(sizeof(Detector) == DETECTOR * 4, "the detector is 8 words");
+
+// What a pair hands to its detector and gets back: the outputs of one push.
+struct Events {
+    int* begin; int* end; float* total; float* mean;           // this pair's `cap` slots
+    int cap, count;                                            // count: emitted in this push, written or not
+};
+
+__device__ __forceinline__ void emit(Detector& det, Events& out) {
+    if (out.count < out.cap) {
+        out.begin[out.count] = det.begin;
+        out.end[out.count] = det.end;
+        out.total[out.count] = det.total;
+        out.mean[out.count] = det.mean;
+    }
+    ++out.count;
+    ++det.events;
+    det.taken = det.end;
+    det.begin = -1;
 }
 
-// The search programme of one pair with S states per lane: `programme` with begins.  Wave-uniform control flow.
-template <int S>
+// one frame of the detector: t is the absolute frame, (sum, first) its curve values
+__device__ __forceinline__ void detect(Detector& det, Events& out, int t, float sum, int first, float threshold,
+                                       int patience) {
+    if (det.begin >= 0 && t - (det.end - 1) > patience) emit(det, out);
+    if (first < 0 || first < det.taken) return;
+    const float value = sum / (float)(t - first + 1);
+    if (!(value >= threshold)) return;
+    if (det.begin >= 0) {
+        if (first < det.end) {                                 // the spans overlap: the better one stays, ties to the later
+            if (!(value >= det.mean)) return;
+        } else {
+            emit(det, out);
+        }
+    }
+    det.begin = first;
+    det.end = t + 1;
+    det.total = sum;
+    det.mean = value;
+}
+
+// What a push of a live search carries into the search of one pair and out of it again.
+struct Carry {
+    float* d; int* b;                         // the pair's strips between pushes: 64 * S words each
+    int base;                                 // the stream's position: frame t of the push is frame base + t of the stream
+    Detector* det; Events* out;               // the pair's detector, run by the lane of state N-1, and this push's events
+    float threshold; int patience;
+};
+
+// The search programme of one pair with S states per lane: `programme` with begins.  Live: one push of T frames of a
+// stream: the strips come from `live` and go back there (the states at or above N run along as ever), frames count
+// from the stream's position, the curve is written only if asked for, and the lane of state N-1 runs the detector.
+// Otherwise `live` is unused: every state starts at -inf / -1 and frames count from 0.  One body, so the pushes of a
+// stream give the curve of the whole recording bit for bit.  Wave-uniform control flow but for that lane's part.
+template <int S, bool Live>
 __device__ __forceinline__ void search_strips(const float4* __restrict__ src, int T, int N, const int* __restrict__ sym,
-                                              float* __restrict__ totals, int* __restrict__ begins,
+                                              float* __restrict__ totals, int* __restrict__ begins, const Carry& live,
                                               float4 (&stage)[2][CHUNK_VEC], int lane)
 {
     int s[S], b[S]; float d[S];
@@ -601,59 +636,41 @@ __device__ __forceinline__ void search_strips(const float4* __restrict__ src, in
     for (int k = 0; k < S; ++k) {
         const int n = lane * S + k;
         s[k] = n < N ? sym[n] : 0;                             // states at or above N run along on phoneme 0, unread
-        d[k] = -INFINITY;
-        b[k] = -1;
+        d[k] = Live ? live.d[n] : -INFINITY;
+        b[k] = Live ? live.b[n] : -1;
     }
     const int last = (N - 1) / S, place = (N - 1) % S;         // the lane of state N-1 and its place in the strip
-    float4 next[FETCH];
-    fetch(src, 0, T, lane, next);
-    stash(stage[0], lane, next);
-    __syncthreads();
-    int buf = 0;
-    for (int t0 = 0; t0 < T; t0 += CHUNK, buf ^= 1) {
-        fetch(src, t0 + CHUNK, T, lane, next);                 // in flight while this chunk is consumed
-        const float* e = reinterpret_cast<const float*>(stage[buf]);
-        const int count = min(CHUNK, T - t0);
-        float cur[S];                                          // frame t's emissions, read one frame ahead of their use
-        {
-            const float top = e[NP];
-#pragma unroll
-            for (int k = 0; k < S; ++k) cur[k] = e[s[k]] - top;
+    const int base = Live ? live.base : 0;
+    WALK_FRAMES(S, true, t, cur,
+        // the state below the strip; below state 0 the origin: 0, beginning at this frame, at every frame
+        const float below = lane_up(d[S - 1], 0.f);
+        const int origin = lane_up(b[S - 1], base + t);
+        _Pragma("unroll") for (int k = S - 1; k >= 0; --k) {   // downwards: d[k - 1] and b[k - 1] are still frame t-1's
+            const float stay = d[k]; const float from = k ? d[k - 1] : below;
+            const int source = k ? b[k - 1] : origin;
+            const bool advance = from > stay;
+            d[k] = cur[k] + (advance ? from : stay);           // -inf + finite = -inf: never NaN
+            b[k] = advance ? source : b[k];
         }
-        for (int u = 0; u < count; ++u) {
-            const int t = t0 + u;
-            const float* ahead = e + min(u + 1, CHUNK - 1) * PREP;       // (the last one re-reads a row: unused)
-            const float top = ahead[NP];
-            float coming[S];
-#pragma unroll
-            for (int k = 0; k < S; ++k) coming[k] = ahead[s[k]] - top;
-            // the state below the strip; below state 0 the origin: 0, beginning at this frame, at every frame
-            const float below = lane_up(d[S - 1], 0.f);
-            const int origin = lane_up_int(b[S - 1], t);
-#pragma unroll
-            for (int k = S - 1; k >= 0; --k) {                 // downwards: d[k - 1] and b[k - 1] are still frame t-1's
-                const float stay = d[k], from = k ? d[k - 1] : below;
-                const int source = k ? b[k - 1] : origin;
-                const bool advance = from > stay;
-                d[k] = cur[k] + (advance ? from : stay);       // -inf + finite = -inf: never NaN
-                b[k] = advance ? source : b[k];
+        if (lane == last) {
+            float end = d[0];
+            int first = b[0];
+            _Pragma("unroll") for (int q = 1; q < S; ++q) {
+                end = place == q ? d[q] : end;
+                first = place == q ? b[q] : first;
             }
-            if (lane == last) {
-                float end = d[0];
-                int first = b[0];
-#pragma unroll
-                for (int q = 1; q < S; ++q) {
-                    end = place == q ? d[q] : end;
-                    first = place == q ? b[q] : first;
-                }
+            if (!Live || totals) {
                 totals[t] = end;
                 begins[t] = first;
             }
+            if (Live) detect(*live.det, *live.out, base + t, end, first, live.threshold, live.patience);
+        })
+    if (Live) {
 #pragma unroll
-            for (int k = 0; k < S; ++k) cur[k] = coming[k];
+        for (int k = 0; k < S; ++k) {
+            live.d[lane * S + k] = d[k];
+            live.b[lane * S + k] = b[k];
         }
-        stash(stage[buf ^ 1], lane, next);
-        __syncthreads();
     }
 }
 
@@ -672,18 +689,14 @@ __global__ __launch_bounds__(64) void search_programme(const float* __restrict__
     const int T = lengths[item], N = phoneme_lengths[query];
     const int* sym = phonemes + (size_t)query * max_phonemes;
     bool fine = T >= 1 && T <= frames && N >= 1 && N <= max_phonemes;
-    if (fine) {
-        bool bad = false;
-        for (int n = lane; n < N; n += 64) bad |= (unsigned)sym[n] >= (unsigned)NP;
-        fine = !__any(bad);
-    }
+    if (fine) fine = symbols_fine(sym, N, lane);
     if (lane == 0) count[pair] = fine ? 0 : -1;
     if (!fine) return;                                         // (uniform)
     const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
     float* out_totals = totals + pair * frames;
     int* out_begins = begins + pair * frames;
-    if (N <= 64) search_strips<1>(src, T, N, sym, out_totals, out_begins, stage, lane);
-    else search_strips<4>(src, T, N, sym, out_totals, out_begins, stage, lane);
+    if (N <= 64) search_strips<1, false>(src, T, N, sym, out_totals, out_begins, Carry{}, stage, lane);
+    else search_strips<4, false>(src, T, N, sym, out_totals, out_begins, Carry{}, stage, lane);
 }
 
 constexpr int PICK = 4;                       // end frames per lane in flight in the picker
@@ -784,11 +797,12 @@ __global__ __launch_bounds__(64) void search_pick(int frames, const int* __restr
 //   flush emits the pending hit, if any, and sets taken; the curve state and the position are kept.  reset returns a
 //   stream to position 0, every state -inf / -1, taken = 0 and nothing pending.  Emitted hits are disjoint, come in
 //   stream order and do not depend on how the frames were split into pushes.
+// (Detector, Events, emit and detect stand above, in front of search_strips, the one search body, which runs them.)
 // The caller owns the state: four blocks, each 256-byte aligned: the position of every stream (int32), the detector of
 // every pair (8 words), then d and b of every pair: a whole wave's strips each, 64 words where max_phonemes <= 64 and
 // 256 above, so that a strip is loaded and stored without a mask.  Four kernels beside align_prepare:
-//   search_stream_programme  grid (queries, streams), one wave per pair: the frame loop of search_strips (the same
-//                            staging, gather and strips) between a load and a store of the strip; the origin's begin is
+//   search_stream_programme  grid (queries, streams), one wave per pair: search_strips<S, Live = true>, the body of
+//                            search_programme between a load and a store of the strip; the origin's begin is
 //                            position + t; the detector runs in the lane of state N-1, in registers, right after that
 //                            lane has the frame's two curve values, and stores an event only when it emits one.
 //   search_stream_advance    one thread per stream, after the programme: position += length.  The only writer of a
@@ -799,15 +813,6 @@ __global__ __launch_bounds__(64) void search_pick(int frames, const int* __restr
 struct StreamLayout {
     size_t positions, detectors, totals, begins, bytes;        // byte offsets into the state
 };
-
-constexpr int DETECTOR = 8;                   // words of a pair's detector
-struct Detector {
-    int taken, begin, end;                    // begin = -1: nothing is pending
-    float total, mean;
-    int events;                               // hits emitted since the reset
-    int reserved[2];
-};
-static_assert(sizeof(Detector) == DETECTOR * 4, "the detector is 8 words");
 
 // the saved states of a pair: every lane's strip, for the longest strip a query of this table may have
 __host__ __device__ inline int stream_states(int max_phonemes) { return max_phonemes <= 64 ? 64 : 256; }
@@ -823,124 +828,6 @@ inline StreamLayout stream_layout(int streams, int queries, int max_phonemes) {
     w.begins = at; at = align256(at + pairs * states * sizeof(int));
     w.bytes = at;
     return w;
-}
-
-// What a pair hands to its detector and gets back: the outputs of one push.
-struct Events {
-    int* begin; int* end; float* total; float* mean;           // this pair's `cap` slots
-    int cap, count;                                            // count: emitted in this push, written or not
-};
-
-__device__ __forceinline__ void emit(Detector& det, Events& out) {
-    if (out.count < out.cap) {
-        out.begin[out.count] = det.begin;
-        out.end[out.count] = det.end;
-        out.total[out.count] = det.total;
-        out.mean[out.count] = det.mean;
-    }
-    ++out.count;
-    ++det.events;
-    det.taken = det.end;
-    det.begin = -1;
-}
-
-// one frame of the detector: t is the absolute frame, (sum, first) its curve values
-__device__ __forceinline__ void detect(Detector& det, Events& out, int t, float sum, int first, float threshold,
-                                       int patience) {
-    if (det.begin >= 0 && t - (det.end - 1) > patience) emit(det, out);
-    if (first < 0 || first < det.taken) return;
-    const float value = sum / (float)(t - first + 1);
-    if (!(value >= threshold)) return;
-    if (det.begin >= 0) {
-        if (first < det.end) {                                 // the spans overlap: the better one stays, ties to the later
-            if (!(value >= det.mean)) return;
-        } else {
-            emit(det, out);
-        }
-    }
-    det.begin = first;
-    det.end = t + 1;
-    det.total = sum;
-    det.mean = value;
-}
-
-// search_strips for one push of T frames at position `base`: the strips come from `state_d`, `state_b` (64 * S words
-// each; the states at or above N run along as ever) and go back there; the lane of state N-1 runs the detector.  Wave-uniform control flow but for that lane's part.
-template <int S>
-__device__ __forceinline__ void search_stream_strips(const float4* __restrict__ src, int T, int N, int base,
-                                                     const int* __restrict__ sym, float* __restrict__ state_d,
-                                                     int* __restrict__ state_b, float* __restrict__ totals,
-                                                     int* __restrict__ begins, Detector& det, Events& out,
-                                                     float threshold, int patience, float4 (&stage)[2][CHUNK_VEC],
-                                                     int lane)
-{
-    int s[S], b[S]; float d[S];
-#pragma unroll
-    for (int k = 0; k < S; ++k) {
-        const int n = lane * S + k;
-        s[k] = n < N ? sym[n] : 0;                             // states at or above N run along on phoneme 0, unread
-        d[k] = state_d[n];
-        b[k] = state_b[n];
-    }
-    const int last = (N - 1) / S, place = (N - 1) % S;         // the lane of state N-1 and its place in the strip
-    float4 next[FETCH];
-    fetch(src, 0, T, lane, next);
-    stash(stage[0], lane, next);
-    __syncthreads();
-    int buf = 0;
-    for (int t0 = 0; t0 < T; t0 += CHUNK, buf ^= 1) {
-        fetch(src, t0 + CHUNK, T, lane, next);                 // in flight while this chunk is consumed
-        const float* e = reinterpret_cast<const float*>(stage[buf]);
-        const int count = min(CHUNK, T - t0);
-        float cur[S];                                          // frame t's emissions, read one frame ahead of their use
-        {
-            const float top = e[NP];
-#pragma unroll
-            for (int k = 0; k < S; ++k) cur[k] = e[s[k]] - top;
-        }
-        for (int u = 0; u < count; ++u) {
-            const int t = t0 + u;
-            const float* ahead = e + min(u + 1, CHUNK - 1) * PREP;       // (the last one re-reads a row: unused)
-            const float top = ahead[NP];
-            float coming[S];
-#pragma unroll
-            for (int k = 0; k < S; ++k) coming[k] = ahead[s[k]] - top;
-            // the state below the strip; below state 0 the origin: 0, beginning at this frame, at every frame
-            const float below = lane_up(d[S - 1], 0.f);
-            const int origin = lane_up_int(b[S - 1], base + t);
-#pragma unroll
-            for (int k = S - 1; k >= 0; --k) {                 // downwards: d[k - 1] and b[k - 1] are still frame t-1's
-                const float stay = d[k], from = k ? d[k - 1] : below;
-                const int source = k ? b[k - 1] : origin;
-                const bool advance = from > stay;
-                d[k] = cur[k] + (advance ? from : stay);       // -inf + finite = -inf: never NaN
-                b[k] = advance ? source : b[k];
-            }
-            if (lane == last) {
-                float end = d[0];
-                int first = b[0];
-#pragma unroll
-                for (int q = 1; q < S; ++q) {
-                    end = place == q ? d[q] : end;
-                    first = place == q ? b[q] : first;
-                }
-                if (totals) {
-                    totals[t] = end;
-                    begins[t] = first;
-                }
-                detect(det, out, base + t, end, first, threshold, patience);
-            }
-#pragma unroll
-            for (int k = 0; k < S; ++k) cur[k] = coming[k];
-        }
-        stash(stage[buf ^ 1], lane, next);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < S; ++k) {
-        state_d[lane * S + k] = d[k];
-        state_b[lane * S + k] = b[k];
-    }
 }
 
 // grid (queries, streams), 64 threads.  count = -1 for a pair that cannot be pushed, which touches nothing else; every
@@ -959,11 +846,7 @@ __global__ __launch_bounds__(64) void search_stream_programme(
     const int T = lengths[item], N = phoneme_lengths[query], base = positions[item];
     const int* sym = phonemes + (size_t)query * max_phonemes;
     bool fine = T >= 0 && T <= frames && N >= 1 && N <= max_phonemes && base >= 0 && T <= INT32_MAX - base;
-    if (fine) {
-        bool bad = false;
-        for (int n = lane; n < N; n += 64) bad |= (unsigned)sym[n] >= (unsigned)NP;
-        fine = !__any(bad);
-    }
+    if (fine) fine = symbols_fine(sym, N, lane);
     if (!fine) {                                               // (uniform)
         if (lane == 0) count[pair] = -1;
         return;
@@ -974,15 +857,11 @@ __global__ __launch_bounds__(64) void search_stream_programme(
         const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
         float* out_totals = curve_total ? curve_total + pair * frames : nullptr;
         int* out_begins = curve_total ? curve_begin + pair * frames : nullptr;
-        float* own_d = state_totals + pair * stream_states(max_phonemes);
-        int* own_b = state_begins + pair * stream_states(max_phonemes);
         Detector det = detectors[pair];                        // (every lane reads it; the lane of state N-1 uses it)
-        if (N <= 64)
-            search_stream_strips<1>(src, T, N, base, sym, own_d, own_b, out_totals, out_begins, det, out, threshold,
-                                    patience, stage, lane);
-        else
-            search_stream_strips<4>(src, T, N, base, sym, own_d, own_b, out_totals, out_begins, det, out, threshold,
-                                    patience, stage, lane);
+        const Carry live{state_totals + pair * stream_states(max_phonemes),
+                         state_begins + pair * stream_states(max_phonemes), base, &det, &out, threshold, patience};
+        if (N <= 64) search_strips<1, true>(src, T, N, sym, out_totals, out_begins, live, stage, lane);
+        else search_strips<4, true>(src, T, N, sym, out_totals, out_begins, live, stage, lane);
         if (lane == last) detectors[pair] = det;
     }
     const int events = __shfl(out.count, last);
@@ -1047,30 +926,67 @@ __global__ __launch_bounds__(64) void search_stream_reset(int max_phonemes, cons
     }
 }
 
-// the checks the three stream entries share: the state and its geometry
-int check_stream_state(const char* what, const void* state, int streams, int queries, int max_phonemes) {
-    if (!state || streams <= 0 || queries <= 0 || max_phonemes <= 0)
-        return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
-    if (streams > PPG_SEARCH_MAX_ITEMS)
-        return ppg::fail_message(PPG_EINVAL, "%s: %d streams, at most %d per call", what, streams, PPG_SEARCH_MAX_ITEMS);
+// ---- the rungs the host entries share, in the order every entry takes them.  Each returns PPG_OK or has left its
+// message; nothing is launched before the last of an entry's checks has passed. ----
+
+// the table of queries of a search, whole-recording or live
+int check_queries(const char* what, int queries, int max_phonemes) {
     if (queries > PPG_SEARCH_MAX_QUERIES)
         return ppg::fail_message(PPG_EINVAL, "%s: %d queries, at most %d per call", what, queries,
                                  PPG_SEARCH_MAX_QUERIES);
     if (max_phonemes > PPG_SEARCH_MAX_PHONEMES)
         return ppg::fail_message(PPG_EINVAL, "%s: %d phonemes, at most %d", what, max_phonemes,
                                  PPG_SEARCH_MAX_PHONEMES);
+    return PPG_OK;
+}
+
+// the checks the three stream entries share: the state and its geometry
+int check_stream_state(const char* what, const void* state, int streams, int queries, int max_phonemes) {
+    if (!state || streams <= 0 || queries <= 0 || max_phonemes <= 0)
+        return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (streams > PPG_SEARCH_MAX_ITEMS)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d streams, at most %d per call", what, streams, PPG_SEARCH_MAX_ITEMS);
+    if (const int rc = check_queries(what, queries, max_phonemes)) return rc;
     if (reinterpret_cast<uintptr_t>(state) % 16)
         return ppg::fail_message(PPG_EINVAL, "%s: the state must be 16-byte aligned", what);
     return PPG_OK;
 }
 
-int check_common(const char* what, const void* ppg, int frames, int items, const void* lengths) {
+// the PPGs of a call: alignment and decode take PPG_ALIGN_MAX_*, the search PPG_SEARCH_MAX_*
+int check_common(const char* what, const void* ppg, int frames, int items, const void* lengths,
+                 int max_frames = PPG_ALIGN_MAX_FRAMES, int max_items = PPG_ALIGN_MAX_ITEMS) {
     if (!ppg || !lengths || items <= 0 || frames <= 0) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
-    if (frames > PPG_ALIGN_MAX_FRAMES)
-        return ppg::fail_message(PPG_EINVAL, "%s: %d frames, at most %d", what, frames, PPG_ALIGN_MAX_FRAMES);
-    if (items > PPG_ALIGN_MAX_ITEMS)
-        return ppg::fail_message(PPG_EINVAL, "%s: %d items, at most %d per call", what, items, PPG_ALIGN_MAX_ITEMS);
+    if (frames > max_frames) return ppg::fail_message(PPG_EINVAL, "%s: %d frames, at most %d", what, frames, max_frames);
+    if (items > max_items)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d items, at most %d per call", what, items, max_items);
     return PPG_OK;
+}
+
+// the sizes ppg_align_workspace_bytes and ppg_align_optional_workspace_bytes answer for
+bool align_sizes_fine(int items, int frames, int max_phonemes) {
+    return items > 0 && items <= PPG_ALIGN_MAX_ITEMS && frames > 0 && frames <= PPG_ALIGN_MAX_FRAMES &&
+           max_phonemes > 0 && max_phonemes <= PPG_ALIGN_MAX_PHONEMES;
+}
+
+int check_workspace(const char* what, const void* workspace, size_t bytes, size_t need) {
+    if (bytes < need)
+        return ppg::fail_message(PPG_EINVAL, "%s: workspace of %zu bytes, %zu needed", what, bytes, need);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16)
+        return ppg::fail_message(PPG_EINVAL, "%s: workspace must be 16-byte aligned", what);
+    return PPG_OK;
+}
+
+// the last check of every entry: from here on it launches
+int select_device(int device) {
+    if (hipSetDevice(device) != hipSuccess)
+        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    return PPG_OK;
+}
+
+// what an entry returns after its launches
+int launched(const char* what) {
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "%s: %s", what, hipGetErrorString(he));
 }
 
 }  // namespace
@@ -1078,10 +994,7 @@ int check_common(const char* what, const void* ppg, int frames, int items, const
 extern "C" {
 
 size_t ppg_align_workspace_bytes(int items, int frames, int max_phonemes) {
-    if (items <= 0 || items > PPG_ALIGN_MAX_ITEMS || frames <= 0 || frames > PPG_ALIGN_MAX_FRAMES ||
-        max_phonemes <= 0 || max_phonemes > PPG_ALIGN_MAX_PHONEMES)
-        return 0;
-    return layout(items, frames).bytes;
+    return align_sizes_fine(items, frames, max_phonemes) ? layout(items, frames, false).bytes : 0;
 }
 
 int ppg_align(int device, const float* ppg, int frames, int items, const int32_t* lengths, const int32_t* phonemes,
@@ -1092,13 +1005,9 @@ int ppg_align(int device, const float* ppg, int frames, int items, const int32_t
         return ppg::fail_message(PPG_EINVAL, "align: bad argument");
     if (max_phonemes > PPG_ALIGN_MAX_PHONEMES)
         return ppg::fail_message(PPG_EINVAL, "align: %d phonemes, at most %d", max_phonemes, PPG_ALIGN_MAX_PHONEMES);
-    const Layout w = layout(items, frames);
-    if (workspace_bytes < w.bytes)
-        return ppg::fail_message(PPG_EINVAL, "align: workspace of %zu bytes, %zu needed", workspace_bytes, w.bytes);
-    if (reinterpret_cast<uintptr_t>(workspace) % 16)
-        return ppg::fail_message(PPG_EINVAL, "align: workspace must be 16-byte aligned");
-    if (hipSetDevice(device) != hipSuccess)
-        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    const Layout w = layout(items, frames, false);
+    if (const int rc = check_workspace("align", workspace, workspace_bytes, w.bytes)) return rc;
+    if (const int rc = select_device(device)) return rc;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     float* logp = reinterpret_cast<float*>(ws + w.logp);
@@ -1110,15 +1019,11 @@ int ppg_align(int device, const float* ppg, int frames, int items, const int32_t
                        phoneme_lengths, total, starts);
     hipLaunchKernelGGL(align_score, dim3((max_phonemes + 63) / 64, items), dim3(64), 0, s, logp, frames, lengths,
                        phonemes, max_phonemes, phoneme_lengths, total, starts, score, gop);
-    const hipError_t he = hipGetLastError();
-    return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "align: %s", hipGetErrorString(he));
+    return launched("align");
 }
 
 size_t ppg_align_optional_workspace_bytes(int items, int frames, int max_phonemes) {
-    if (items <= 0 || items > PPG_ALIGN_MAX_ITEMS || frames <= 0 || frames > PPG_ALIGN_MAX_FRAMES ||
-        max_phonemes <= 0 || max_phonemes > PPG_ALIGN_MAX_PHONEMES)
-        return 0;
-    return optional_layout(items, frames).bytes;
+    return align_sizes_fine(items, frames, max_phonemes) ? layout(items, frames, true).bytes : 0;
 }
 
 int ppg_align_optional(int device, const float* ppg, int frames, int items, const int32_t* lengths,
@@ -1131,14 +1036,9 @@ int ppg_align_optional(int device, const float* ppg, int frames, int items, cons
     if (max_phonemes > PPG_ALIGN_MAX_PHONEMES)
         return ppg::fail_message(PPG_EINVAL, "align_optional: %d phonemes, at most %d", max_phonemes,
                                  PPG_ALIGN_MAX_PHONEMES);
-    const OptionalLayout w = optional_layout(items, frames);
-    if (workspace_bytes < w.bytes)
-        return ppg::fail_message(PPG_EINVAL, "align_optional: workspace of %zu bytes, %zu needed", workspace_bytes,
-                                 w.bytes);
-    if (reinterpret_cast<uintptr_t>(workspace) % 16)
-        return ppg::fail_message(PPG_EINVAL, "align_optional: workspace must be 16-byte aligned");
-    if (hipSetDevice(device) != hipSuccess)
-        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    const Layout w = layout(items, frames, true);
+    if (const int rc = check_workspace("align_optional", workspace, workspace_bytes, w.bytes)) return rc;
+    if (const int rc = select_device(device)) return rc;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     float* logp = reinterpret_cast<float*>(ws + w.logp);
@@ -1152,20 +1052,17 @@ int ppg_align_optional(int device, const float* ppg, int frames, int items, cons
                        max_phonemes, phoneme_lengths, total, ends, starts);
     hipLaunchKernelGGL(align_score_optional, dim3((max_phonemes + 63) / 64, items), dim3(64), 0, s, logp, frames,
                        lengths, phonemes, max_phonemes, phoneme_lengths, total, starts, score, gop);
-    const hipError_t he = hipGetLastError();
-    return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "align_optional: %s", hipGetErrorString(he));
+    return launched("align_optional");
 }
 
 int ppg_decode(int device, const float* ppg, int frames, int items, const int32_t* lengths, int32_t* phonemes,
                int32_t* starts, int32_t* runs, void* stream) {
     if (const int rc = check_common("decode", ppg, frames, items, lengths)) return rc;
     if (!phonemes || !starts || !runs) return ppg::fail_message(PPG_EINVAL, "decode: bad argument");
-    if (hipSetDevice(device) != hipSuccess)
-        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    if (const int rc = select_device(device)) return rc;
     hipLaunchKernelGGL(decode_runs, dim3(items), dim3(64), 0, static_cast<hipStream_t>(stream), ppg, frames, lengths,
                        phonemes, starts, runs);
-    const hipError_t he = hipGetLastError();
-    return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "decode: %s", hipGetErrorString(he));
+    return launched("decode");
 }
 
 size_t ppg_search_workspace_bytes(int items, int frames, int queries) {
@@ -1179,30 +1076,20 @@ int ppg_search(int device, const float* ppg, int frames, int items, const int32_
                int max_phonemes, int queries, const int32_t* phoneme_lengths, int top, float threshold, int32_t* begin,
                int32_t* end, float* total, float* mean, int32_t* count, float* curve_total, int32_t* curve_begin,
                void* workspace, size_t workspace_bytes, void* stream) {
-    if (!ppg || !lengths || !phonemes || !phoneme_lengths || !begin || !end || !total || !mean || !count ||
-        !workspace || items <= 0 || frames <= 0 || queries <= 0 || max_phonemes <= 0)
+    if (!phonemes || !phoneme_lengths || !begin || !end || !total || !mean || !count || !workspace || queries <= 0 ||
+        max_phonemes <= 0)
         return ppg::fail_message(PPG_EINVAL, "search: bad argument");
-    if (frames > PPG_SEARCH_MAX_FRAMES)
-        return ppg::fail_message(PPG_EINVAL, "search: %d frames, at most %d", frames, PPG_SEARCH_MAX_FRAMES);
-    if (items > PPG_SEARCH_MAX_ITEMS)
-        return ppg::fail_message(PPG_EINVAL, "search: %d items, at most %d per call", items, PPG_SEARCH_MAX_ITEMS);
-    if (queries > PPG_SEARCH_MAX_QUERIES)
-        return ppg::fail_message(PPG_EINVAL, "search: %d queries, at most %d per call", queries,
-                                 PPG_SEARCH_MAX_QUERIES);
-    if (max_phonemes > PPG_SEARCH_MAX_PHONEMES)
-        return ppg::fail_message(PPG_EINVAL, "search: %d phonemes, at most %d", max_phonemes, PPG_SEARCH_MAX_PHONEMES);
+    if (const int rc = check_common("search", ppg, frames, items, lengths, PPG_SEARCH_MAX_FRAMES, PPG_SEARCH_MAX_ITEMS))
+        return rc;
+    if (const int rc = check_queries("search", queries, max_phonemes)) return rc;
     if (top < 1 || top > PPG_SEARCH_MAX_HITS)
         return ppg::fail_message(PPG_EINVAL, "search: top = %d, must be 1 .. %d", top, PPG_SEARCH_MAX_HITS);
     if (threshold != threshold) return ppg::fail_message(PPG_EINVAL, "search: the threshold is NaN");
     if (!curve_total != !curve_begin)
         return ppg::fail_message(PPG_EINVAL, "search: curve_total and curve_begin go together");
     const SearchLayout w = search_layout(items, frames, queries);
-    if (workspace_bytes < w.bytes)
-        return ppg::fail_message(PPG_EINVAL, "search: workspace of %zu bytes, %zu needed", workspace_bytes, w.bytes);
-    if (reinterpret_cast<uintptr_t>(workspace) % 16)
-        return ppg::fail_message(PPG_EINVAL, "search: workspace must be 16-byte aligned");
-    if (hipSetDevice(device) != hipSuccess)
-        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    if (const int rc = check_workspace("search", workspace, workspace_bytes, w.bytes)) return rc;
+    if (const int rc = select_device(device)) return rc;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     float* logp = reinterpret_cast<float*>(ws + w.logp);
@@ -1213,8 +1100,7 @@ int ppg_search(int device, const float* ppg, int frames, int items, const int32_
                        max_phonemes, phoneme_lengths, totals, begins, count);
     hipLaunchKernelGGL(search_pick, dim3(queries, items), dim3(64), 0, s, frames, lengths, phoneme_lengths, top,
                        threshold, totals, begins, begin, end, total, mean, count, curve_total, curve_begin);
-    const hipError_t he = hipGetLastError();
-    return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "search: %s", hipGetErrorString(he));
+    return launched("search");
 }
 
 size_t ppg_search_stream_state_bytes(int streams, int queries, int max_phonemes) {
@@ -1228,23 +1114,20 @@ size_t ppg_search_stream_workspace_bytes(int streams, int frames, int queries) {
     if (streams <= 0 || streams > PPG_SEARCH_MAX_ITEMS || frames <= 0 || frames > PPG_SEARCH_MAX_FRAMES ||
         queries <= 0 || queries > PPG_SEARCH_MAX_QUERIES)
         return 0;
-    return align256((size_t)streams * frames * PREP * sizeof(float));
+    return prepared_bytes(streams, frames);
 }
 
 int ppg_search_stream_reset(int device, void* state, int streams, int queries, int max_phonemes, const int32_t* which,
                             void* stream) {
     if (const int rc = check_stream_state("search_stream_reset", state, streams, queries, max_phonemes)) return rc;
-    if (hipSetDevice(device) != hipSuccess)
-        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    if (const int rc = select_device(device)) return rc;
     const StreamLayout w = stream_layout(streams, queries, max_phonemes);
     char* st = static_cast<char*>(state);
     hipLaunchKernelGGL(search_stream_reset, dim3(queries, streams), dim3(64), 0, static_cast<hipStream_t>(stream),
                        max_phonemes, which, reinterpret_cast<int*>(st + w.positions),
                        reinterpret_cast<Detector*>(st + w.detectors), reinterpret_cast<float*>(st + w.totals),
                        reinterpret_cast<int*>(st + w.begins));
-    const hipError_t he = hipGetLastError();
-    return he == hipSuccess ? PPG_OK
-                            : ppg::fail_message(PPG_EDEVICE, "search_stream_reset: %s", hipGetErrorString(he));
+    return launched("search_stream_reset");
 }
 
 int ppg_search_stream_push(int device, void* state, const float* ppg, int frames, int streams, const int32_t* lengths,
@@ -1264,14 +1147,10 @@ int ppg_search_stream_push(int device, void* state, const float* ppg, int frames
     if (cap < 1) return ppg::fail_message(PPG_EINVAL, "search_stream_push: cap = %d, must be at least 1", cap);
     if (!curve_total != !curve_begin)
         return ppg::fail_message(PPG_EINVAL, "search_stream_push: curve_total and curve_begin go together");
-    const size_t need = align256((size_t)streams * frames * PREP * sizeof(float));
-    if (workspace_bytes < need)
-        return ppg::fail_message(PPG_EINVAL, "search_stream_push: workspace of %zu bytes, %zu needed", workspace_bytes,
-                                 need);
-    if (reinterpret_cast<uintptr_t>(workspace) % 16)
-        return ppg::fail_message(PPG_EINVAL, "search_stream_push: workspace must be 16-byte aligned");
-    if (hipSetDevice(device) != hipSuccess)
-        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    if (const int rc = check_workspace("search_stream_push", workspace, workspace_bytes,
+                                       prepared_bytes(streams, frames)))
+        return rc;
+    if (const int rc = select_device(device)) return rc;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const StreamLayout w = stream_layout(streams, queries, max_phonemes);
     char* st = static_cast<char*>(state);
@@ -1284,8 +1163,7 @@ int ppg_search_stream_push(int device, void* state, const float* ppg, int frames
                        patience, cap, begin, end, total, mean, count, curve_total, curve_begin);
     hipLaunchKernelGGL(search_stream_advance, dim3((streams + 63) / 64), dim3(64), 0, s, streams, frames, lengths,
                        positions);
-    const hipError_t he = hipGetLastError();
-    return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "search_stream_push: %s", hipGetErrorString(he));
+    return launched("search_stream_push");
 }
 
 int ppg_search_stream_flush(int device, void* state, int streams, int queries, int max_phonemes, const int32_t* which,
@@ -1293,17 +1171,14 @@ int ppg_search_stream_flush(int device, void* state, int streams, int queries, i
     if (!begin || !end || !total || !mean || !count)
         return ppg::fail_message(PPG_EINVAL, "search_stream_flush: bad argument");
     if (const int rc = check_stream_state("search_stream_flush", state, streams, queries, max_phonemes)) return rc;
-    if (hipSetDevice(device) != hipSuccess)
-        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    if (const int rc = select_device(device)) return rc;
     const StreamLayout w = stream_layout(streams, queries, max_phonemes);
     const size_t pairs = (size_t)streams * queries;
     hipLaunchKernelGGL(search_stream_flush, dim3((unsigned)((pairs + 63) / 64)), dim3(64), 0,
                        static_cast<hipStream_t>(stream), streams, queries, which,
                        reinterpret_cast<Detector*>(static_cast<char*>(state) + w.detectors), begin, end, total, mean,
                        count);
-    const hipError_t he = hipGetLastError();
-    return he == hipSuccess ? PPG_OK
-                            : ppg::fail_message(PPG_EDEVICE, "search_stream_flush: %s", hipGetErrorString(he));
+    return launched("search_stream_flush");
 }
 
 }  // extern "C"
