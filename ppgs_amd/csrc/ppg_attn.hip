@@ -498,19 +498,6 @@ hipError_t launch_attn_p(const AttnArgs& a, int nitems, int heads, int head_dim,
 
 }  // namespace
 
-// -DPPG_ONLY_BF16: kernel experiments build only the bf16 instantiations (a third of the compile time)
-#ifdef PPG_ONLY_BF16
-#define PPG_OTHER_PRECISIONS 0
-#else
-#define PPG_OTHER_PRECISIONS 1
-#endif
-// (-DPPG_ONLY_BF16 -DPPG_WITH_X2: bf16 and the split-precision mode)
-#if PPG_OTHER_PRECISIONS || defined(PPG_WITH_X2)
-#define PPG_X2 1
-#else
-#define PPG_X2 0
-#endif
-
 namespace ppg {
 
 int attn_query_tile(int head_dim) { return head_dim == 128 ? 128 : 64; }   // (d = 64 and d = 256: 16 queries per wave)

@@ -87,7 +87,7 @@ static void choose_ffn_tiling(const PpgEngine* e, int M, int* nt_out, int* split
         if (best > 1) { nt = max_nt; splits = best; }
     }
     if (e->ffn_splits_forced > 0 && e->ffn_fused) { nt = max_nt; splits = e->ffn_splits_forced; }
-    // mixed tiling (160-token workgroups, ppg_kernels.hip ffn_mixed_kernel): 2.5 blocks of
+    // mixed tiling (160-token workgroups, ppg_ffn.h ffn_mixed_kernel): 2.5 blocks of
     // MFMA work per wave and chunk instead of nt; worth it when it saves a round or
     // shortens the one round there is (C2: 256 workgroups on 256 CUs instead of 214 larger ones)
     if (splits == 1 && e->ffn_mixed && e->ffn_fused && e->op_fused && e->ffn_nt == 0 &&
@@ -383,7 +383,7 @@ int ppg_engine_create(const PpgConfig* cfg, const PpgWeights* wts, int device, P
         // the unfused launch sequence: Q/K/V, attention, out-projection + LayerNorm, FFN as one launch each
         e->op_fused = false; e->qkv_fused = false; e->ffn_mixed = false; e->ffn_fused = true;
         // hidden 512: the FFN as two GEMMs through a [tokens][ffn] buffer of [32 hi | 32 lo] rows (a chunk of the fused
-        // kernel cannot hold a 32-wide hidden group of both weight tiles: ppg_kernels.hip, launch_linear_x2_nt)
+        // kernel cannot hold a 32-wide hidden group of both weight tiles: ppg_linear.h, launch_linear_x2_nt)
         if (H == 512) e->ffn_fused = false;
     }
     // With the out-projection (or the mixed tiling's hand-off) fused in, the FFN kernel has LDS for fewer hidden

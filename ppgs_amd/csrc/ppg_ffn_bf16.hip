@@ -1,0 +1,4 @@
+// The fused FFN kernels (ppg_ffn.h) in bf16, the mixed tiling among them.
+#include "ppg_ffn.h"
+
+template hipError_t ppg::launch_ffn_p<PrecBF16>(const FfnArgs&, int, hipStream_t);

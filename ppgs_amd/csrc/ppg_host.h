@@ -234,7 +234,7 @@ void dump_timing_stamps(const PpgEngine* e);   // ppg_timing.hip: what the engin
 #endif
 
 int choose_nt(int num_cus, int forced_nt, int M, int max_nt);
-// The fused FFN kernel (ppg_kernels.hip, ffn_body) walks the hidden features in chunks of one 32 KiB W1 tile; a
+// The fused FFN kernel (ppg_ffn.h, ffn_body) walks the hidden features in chunks of one 32 KiB W1 tile; a
 // split-hidden launch gives each of its `splits` workgroups per tile chunks / splits of them, so a split count must
 // divide the chunk count.
 inline int ffn_chunks(int hidden, int ffn, int sz) { return ffn / (32768 / (hidden * sz)); }

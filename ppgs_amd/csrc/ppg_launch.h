@@ -1,4 +1,6 @@
-// Host-callable launchers implemented in ppg_kernels.hip / ppg_frontend.hip.
+// Host-callable launchers of the kernels; each is implemented in the unit that holds its kernels (named at the
+// declaration where the name does not say it: launch_gather / launch_fill in ppg_gather.hip, launch_linear in
+// ppg_linear.hip, launch_ffn in ppg_ffn.hip, launch_attn in ppg_attn.hip).
 #pragma once
 
 #include <algorithm>
@@ -23,6 +25,20 @@ inline bool env_experiment_set(const char* name) { return getenv(name) != nullpt
 #else
 inline int env_experiment(const char*, int dflt) { return dflt; }
 inline bool env_experiment_set(const char*) { return false; }
+#endif
+
+// -DPPG_ONLY_BF16: kernel experiments build only the bf16 instantiations (the Makefile leaves the other precisions'
+// units out)
+#ifdef PPG_ONLY_BF16
+#define PPG_OTHER_PRECISIONS 0
+#else
+#define PPG_OTHER_PRECISIONS 1
+#endif
+// (-DPPG_ONLY_BF16 -DPPG_WITH_X2: bf16 and the split-precision mode)
+#if PPG_OTHER_PRECISIONS || defined(PPG_WITH_X2)
+#define PPG_X2 1
+#else
+#define PPG_X2 0
 #endif
 
 int attn_query_tile(int head_dim);   // queries per attention workgroup

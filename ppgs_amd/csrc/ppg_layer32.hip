@@ -11,7 +11,7 @@
 //    matrix pipe idles (one 512-register wave per SIMD), 21 % of the token-split
 //    kernel's chunk loop -- a plain global_load_dwordx4 into registers between two
 //    32x32 MFMAs costs next to nothing.
-// So the operands trade places against ffn_body (ppg_kernels.hip): the four waves
+// So the operands trade places against ffn_body (ppg_ffn.h): the four waves
 // (one per SIMD) all work on ALL 160 tokens -- 5 blocks of 32, the MFMA's N -- and
 // split the FEATURES: wave w owns output features 64w..64w+63 of every 256-wide
 // result and hidden rows 32w..32w+31 of every 128-hidden chunk.  Weights never touch

@@ -15,12 +15,6 @@
 
 #include <utility>
 
-#ifdef PPG_ONLY_BF16
-#define PPG_OTHER_PRECISIONS 0
-#else
-#define PPG_OTHER_PRECISIONS 1
-#endif
-
 namespace {
 
 constexpr int OT = 64;                  // tokens per tile (16 per wave)

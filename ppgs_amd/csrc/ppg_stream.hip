@@ -100,7 +100,7 @@ int ppg_stream_create_batch(PpgEngine* e, int batch, int max_frames, int feature
     // partial sums of the split-hidden FFN launches: [splits][batch * R][H] fp32, at most 256 MiB
     {
         const int chunks = ppg::ffn_chunks(c.hidden_channels, c.ffn_channels, e->sz);    // (a split count must divide them)
-        // (under a row map a split's rows are slot-dense, ceil(map_blocks / 4) * 64 of them -- ppg_kernels.hip, ffn_body's
+        // (under a row map a split's rows are slot-dense, ceil(map_blocks / 4) * 64 of them -- ppg_ffn.h, ffn_body's
         // epilogue and the reduce pass: up to MT rounded up to a whole 64-row workgroup, not MT)
         const size_t per_split = (size_t)round_up(MT, 64) * c.hidden_channels * 4;
         st->max_splits = 1;
