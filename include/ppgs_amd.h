@@ -569,6 +569,62 @@ int ppg_align_optional(int device, const float* ppg, int frames, int items, cons
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Phoneme recognition: what was said -- the best path through the 40 phonemes under a transition model (a switch
+ * penalty, a phone bigram, a hand-built topology).  ppg_decode is the same question without a model: per-frame argmax,
+ * where one frame that flips to a neighbouring vowel splits a phoneme into three runs.  The reference has only that
+ * (ppgs/edit/core.py, argmax + unique_consecutive).
+ *
+ * One utterance: P (40, T), T >= 1; transitions A (40, 40) fp32, A[p, q] the weight of going from p at frame t-1 to q
+ * at frame t (the diagonal: of staying); initial (40,) and final (40,) fp32.  Every entry is finite or -inf (NaN and
+ * +inf are for the caller to refuse: the entry does not read device memory).
+ *   e[t, q] = logf(min(max(P[q, t], 1e-8), 1 - 1e-8))          the prepared frame of ppg_align, the same kernel
+ *   D[0, q] = e[0, q] + initial[q]
+ *   c[p]    = D[t-1, p] + A[p, q]                               one fp32 addition per candidate
+ *   best = c[q], from = q;  for p = 0 .. 39, p != q:  if c[p] > best: best = c[p], from = p
+ *   D[t, q] = e[t, q] + best                                    fp32, in order of t
+ *   end:  F[q] = D[T-1, q] + final[q];  last = the first q with the largest F (strict >, ascending q);  total = F[last]
+ * Comparisons only.  On ties staying beats switching and the lowest predecessor index beats a higher one.  -inf + finite
+ * = -inf and -inf > -inf is false, so a state nothing reaches never gives NaN.
+ * The trace-back from `last` gives one label per frame; the output is the runs of those labels:
+ *   phonemes[r]  the label of run r, r < R;  starts[r] its first frame, starts[0] = 0, starts[R] = T;  runs = R
+ *   score[r]     the mean of e[t, phonemes[r]] over the run, summed in frame order
+ *   gop[r]       the mean over the run of e[t, phonemes[r]] - max_q e[t, q]
+ * score and gop come from the code of ppg_align on the runs as its transcript: where the definitions coincide the bits
+ * do.  With the left-to-right chain of a transcript of distinct phonemes as A (0 for staying in s[n] and for going from
+ * s[n] to s[n+1], initial[s[0]] = final[s[N-1]] = 0, -inf elsewhere) every output is that of ppg_align bit for bit; with
+ * A = 0 the runs are those of ppg_decode wherever every frame's largest posterior is clear of the others.
+ * If every F[q] is -inf the utterance has no path: total = -inf, runs = 0, and nothing else is written.  An item whose
+ * length is outside [1, frames] gets total = NaN and runs = 0 and nothing else.
+ *
+ * ppg_recognize:
+ *   ppg, lengths : as for ppg_align
+ *   transitions  : device fp32 (40, 40), one matrix for the whole call
+ *   initial, final_ : device fp32[40]; NULL means all zeros
+ *   phonemes     : device int32 (items, frames): entries 0 .. R-1 of item b are written
+ *   starts       : device int32 (items, frames + 1): entries 0 .. R are written
+ *   runs         : device int32[items]
+ *   total        : device fp32[items]
+ *   score, gop   : device fp32 (items, frames): entries 0 .. R-1 are written; gop may be NULL
+ *   workspace    : device memory, 16-byte aligned, at least ppg_recognize_workspace_bytes(items, frames) bytes: four
+ *                  blocks, each 256-byte aligned: the prepared frames (176 B per frame), the back-pointers (one byte per
+ *                  state and frame, 64 B per frame, in dwords of four frames), one int32 label per frame, and the end
+ *                  state of every item
+ * Kernel launches on `stream` only: no allocation, synchronisation or copy; every byte a kernel reads was written by an
+ * earlier kernel of the same call, so the workspace needs no clearing.  Calls with workspaces of their own may run
+ * concurrently on several streams.  A batch equals its singles bit for bit.
+ * PPG_EINVAL, with nothing launched, for a NULL required pointer, an unaligned or short workspace, or more than
+ * PPG_RECOGNIZE_MAX_FRAMES frames or PPG_RECOGNIZE_MAX_ITEMS items (ppg_recognize_workspace_bytes, which is host-only,
+ * returns 0 for such arguments).
+ */
+#define PPG_RECOGNIZE_MAX_FRAMES 262144      /* = PPG_SEARCH_MAX_FRAMES: recordings, not only utterances */
+#define PPG_RECOGNIZE_MAX_ITEMS  65535
+size_t ppg_recognize_workspace_bytes(int items, int frames);
+int ppg_recognize(int device, const float* ppg, int frames, int items, const int32_t* lengths,
+                  const float* transitions, const float* initial, const float* final_,
+                  int32_t* phonemes, int32_t* starts, int32_t* runs, float* total, float* score, float* gop,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Phrase search: where in a recording is a phoneme sequence said, and how well (keyword spotting on posteriorgrams).
  * ppg_align pins its transcript to frame 0 and frame T-1; here the match may start and end at any frame.  Not in the
  * reference.

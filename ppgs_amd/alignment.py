@@ -2,7 +2,8 @@
 
 `ppgs_amd.distance` and `ppgs_amd.dtw` say how far apart two pronunciations are.  This module answers the other
 question of pronunciation work: given the PPG and the phonemes the speaker was meant to say, where does each phoneme
-start, and how well was it said?  It runs on the GPU (ppg_align and ppg_decode, ppgs_amd/csrc/ppg_align.hip).
+start, and how well was it said?  It runs on the GPU (ppg_align, ppg_decode and ppg_recognize,
+ppgs_amd/csrc/ppg_align.hip).
 
 For one utterance, PPG P (40, T) and phoneme indices s of length N, 1 <= N <= T:
 
@@ -24,6 +25,28 @@ every phoneme of the sequence gets at least one frame.
     alignment = ppgs_amd.alignment.forced(ppg, ['hh', 'ah', 'l', 'ow'])
     for name, start, end, score, gop in ppgs_amd.alignment.segments(alignment): ...
     free = ppgs_amd.alignment.decode(ppg)            # what the PPG says by itself: runs of the per-frame argmax
+
+Recognition (`recognize`, ppg_recognize): what was said, under a transition model.  `decode` is the per-frame argmax
+cut into runs, and one frame that flips to a neighbouring vowel splits a phoneme into three; `recognize` finds the best
+path through the 40 phonemes given transitions A (40, 40) -- A[p, q] weighs going from p to q, the diagonal staying --
+and weights `initial` and `final` (40,) on the first and the last frame's phoneme, every entry finite or -inf:
+
+    e[t, q] = the log-posterior above, of phoneme q itself
+    D[0, q] = e[0, q] + initial[q]
+    c[p]    = D[t-1, p] + A[p, q]                                one fp32 addition per candidate
+    best = c[q], from = q;  for p = 0 .. 39, p != q:  if c[p] > best: best = c[p], from = p
+    D[t, q] = e[t, q] + best                                     fp32, in order of t
+    F[q] = D[T-1, q] + final[q];  last = the first q with the largest F;  total = F[last]
+
+Comparisons only: on ties staying beats switching and the lowest predecessor wins.  The trace-back from `last` labels
+every frame; the result is the runs of those labels with `forced`'s score and gop per run, up to 262144 frames.  `forced`
+and `decode` are the two corners of it: under `chain(s)`, the left-to-right topology of a transcript of distinct
+phonemes, it is `forced(ppg, s)` bit for bit, and with A = 0 it is `decode` wherever every frame's winner is clear.
+
+    said = ppgs_amd.alignment.recognize(ppg, penalty=4.)                     # a switch has to pay for itself
+    A, initial, final = ppgs_amd.alignment.bigram(lexicon_sequences)         # or a phone bigram
+    said = ppgs_amd.alignment.recognize(ppg, transitions=A, initial=initial, final=final)
+    for name, start, end, score, gop in ppgs_amd.alignment.segments(said): ...
 
 Optional phonemes (`forced(..., optional=flags)`, ppg_align_optional): a speaker pauses between words wherever they
 like, and drops a final consonant or a schwa.  flags[n] lets the path leave phoneme n out:
@@ -78,12 +101,14 @@ from .phonemes import PHONEMES, PHONEME_TO_INDEX_MAPPING
 
 MAX_FRAMES = engine.ALIGN_MAX_FRAMES
 MAX_PHONEMES = engine.ALIGN_MAX_PHONEMES
+RECOGNIZE_MAX_FRAMES = engine.RECOGNIZE_MAX_FRAMES
 SEARCH_MAX_FRAMES = engine.SEARCH_MAX_FRAMES
 SEARCH_MAX_PHONEMES = engine.SEARCH_MAX_PHONEMES
 SEARCH_MAX_HITS = engine.SEARCH_MAX_HITS
 
 Alignment = collections.namedtuple('Alignment', ['phonemes', 'starts', 'total', 'score', 'gop'])
 Decoding = collections.namedtuple('Decoding', ['phonemes', 'starts'])
+Recognition = collections.namedtuple('Recognition', Alignment._fields)
 Hits = collections.namedtuple('Hits', ['phonemes', 'begin', 'end', 'total', 'mean', 'count', 'curve'])
 
 
@@ -353,6 +378,126 @@ def decode(ppg, lengths=None):
     if not batched:
         return Decoding(phonemes[0, :runs[0]], starts[0, :runs[0] + 1])
     return Decoding([phonemes[b, :r] for b, r in enumerate(runs)], [starts[b, :r + 1] for b, r in enumerate(runs)])
+
+
+def switch_penalty(penalty):
+    """The simplest transition model: (40, 40) fp32, 0 for staying in a phoneme and -penalty for every switch.
+    `penalty` >= 0 and finite; in units of log-posterior, it is what a phoneme has to gain over its run's frames to be
+    worth two switches.  Host only."""
+    if isinstance(penalty, bool) or not isinstance(penalty, (int, float)) or not 0 <= penalty < math.inf:
+        raise ValueError(f'a switch penalty must be a finite number >= 0, got {penalty!r}')
+    count = len(PHONEMES)
+    matrix = torch.full((count, count), -float(penalty), dtype=torch.float32)
+    matrix.fill_diagonal_(0.)
+    return matrix
+
+
+def bigram(sequences, smoothing=1.0, scale=1.0):
+    """A phone bigram from phoneme sequences (names or indices, e.g. what `decode` or a lexicon gives):
+    (transitions (40, 40), initial (40,), final (40,)), fp32.  With count[p, q] the number of times q follows p in a
+    sequence, row p of transitions holds scale * log((count[p, q] + smoothing) / (sum_q count[p, q] + 40 * smoothing));
+    initial and final are the same from the counts of first and of last phonemes.  smoothing = 0 gives -inf for what
+    was never seen; a row without counts is then an error.  Computed in float64, rounded once.  Host only."""
+    for name, value in (('smoothing', smoothing), ('scale', scale)):
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0 <= value < math.inf:
+            raise ValueError(f'{name} must be a finite number >= 0, got {value!r}')
+    if scale == 0:
+        raise ValueError('scale must be positive: 0 would weigh nothing (and 0 * -inf is NaN)')
+    if isinstance(sequences, (str, bytes)) or not isinstance(sequences, (list, tuple)) or len(sequences) < 1:
+        raise ValueError('a bigram takes a non-empty list of phoneme sequences')
+    count = len(PHONEMES)
+    pairs = torch.zeros((count, count), dtype=torch.float64)
+    first, last = torch.zeros(count, dtype=torch.float64), torch.zeros(count, dtype=torch.float64)
+    for sequence in sequences:
+        sequence = _sequence(sequence)
+        if not sequence:
+            raise ValueError('an empty phoneme sequence has no first or last phoneme')
+        first[sequence[0]] += 1
+        last[sequence[-1]] += 1
+        for p, q in zip(sequence, sequence[1:]):
+            pairs[p, q] += 1
+
+    def weights(counts, what):
+        sums = counts.sum(-1, keepdim=True) + count * smoothing
+        if bool((sums == 0).any()):
+            empty = [PHONEMES[p] for p in torch.nonzero(sums.reshape(-1) == 0).reshape(-1).tolist()]
+            raise ValueError(f'{what} without counts and without smoothing: ' +
+                             (', '.join(empty) if counts.dim() == 2 else 'no sequences'))
+        return (scale * torch.log((counts + smoothing) / sums)).to(torch.float32)
+    return weights(pairs, 'rows'), weights(first, 'first phonemes'), weights(last, 'last phonemes')
+
+
+def chain(phonemes):
+    """The left-to-right topology over a sequence s of N distinct phonemes: (transitions, initial, final) with
+    transitions[s[n], s[n]] = transitions[s[n], s[n + 1]] = 0, initial[s[0]] = final[s[N - 1]] = 0 and -inf everywhere
+    else.  `recognize` under it is `forced(ppg, s)` bit for bit: this is how the two relate (and the test of it).  A
+    phoneme cannot come twice, for a state is a phoneme here.  Host only."""
+    sequence = _sequence(phonemes)
+    if not sequence:
+        raise ValueError('a chain takes at least one phoneme')
+    if len(set(sequence)) != len(sequence):
+        raise ValueError('a chain takes distinct phonemes: a state of the recogniser is a phoneme, not a position')
+    count = len(PHONEMES)
+    transitions = torch.full((count, count), -math.inf, dtype=torch.float32)
+    initial, final = torch.full((count,), -math.inf), torch.full((count,), -math.inf)
+    for n, p in enumerate(sequence):
+        transitions[p, p] = 0.
+        if n + 1 < len(sequence):
+            transitions[p, sequence[n + 1]] = 0.
+    initial[sequence[0]] = 0.
+    final[sequence[-1]] = 0.
+    return transitions, initial, final
+
+
+def _weights(tensor, shape, name):
+    """A table of weights of `recognize`: fp32, every entry finite or -inf."""
+    if not torch.is_tensor(tensor) or tuple(tensor.shape) != shape or tensor.is_complex() or tensor.dtype == torch.bool:
+        raise ValueError(f'{name} must be a {shape} tensor of weights, got {tuple(getattr(tensor, "shape", ()))} '
+                         f'{getattr(tensor, "dtype", type(tensor).__name__)}')
+    tensor = tensor.detach().to(torch.float32)
+    if bool((torch.isnan(tensor) | (tensor == math.inf)).any()):
+        raise ValueError(f'{name} holds NaN or +inf: a weight is finite or -inf')
+    return tensor
+
+
+def recognize(ppg, lengths=None, transitions=None, initial=None, final=None, penalty=None, gop=True):
+    """What was said, under a transition model: Recognition(phonemes, starts, total, score, gop), the runs of the best
+    path through the 40 phonemes (see the module's text), where `decode` gives the runs of the per-frame argmax.
+
+    `ppg` is (40, T) or a batch (B, 40, T) padded to the longest item with `lengths` per item (the padding is never
+    read), up to 262144 frames.  `transitions` is a (40, 40) tensor on the CPU or the device: transitions[p, q] is the
+    weight of going from p to q, the diagonal that of staying; `initial` and `final` (40,) weigh the first and the last
+    frame's phoneme (None: zeros).  Every entry is finite or -inf.  `penalty=c` is shorthand for
+    `transitions=switch_penalty(c)`; one of the two must be given, and only one.  One model serves the whole batch.
+    One utterance returns device tensors: phonemes (R,) int32, starts (R + 1,) int32, total 0-d, score and gop (R,)
+    fp32; a batch returns lists of B such tensors and total (B,), as `forced` does, and equals its single calls bit for
+    bit.  gop=False skips that sum and returns None for it.  An utterance that no path fits (the model forbids every
+    way through it) has no phonemes, starts = [0] and total = -inf.  `segments`, `frame_labels` and `word_segments`
+    take the result as they take an Alignment."""
+    batched, batch, frames = _ppg(ppg, RECOGNIZE_MAX_FRAMES, 'recognize')
+    if not batched and lengths is not None:
+        raise ValueError('lengths go with a batch: slice a single PPG instead')
+    lengths = _lengths(lengths, batch, frames)
+    if (transitions is None) == (penalty is None):
+        raise ValueError('recognize takes either transitions or penalty: one of them, not both')
+    if transitions is None:
+        transitions = switch_penalty(penalty)
+    count = len(PHONEMES)
+    transitions = _weights(transitions, (count, count), 'transitions')
+    initial = None if initial is None else _weights(initial, (count,), 'initial')
+    final = None if final is None else _weights(final, (count,), 'final')
+    device = core.device_for(None, ppg)
+    x = ppg.to(device)
+    phonemes, starts, runs, total, score, below = engine.recognize_items(
+        x if batched else x[None], lengths, transitions.to(device), None if initial is None else initial.to(device),
+        None if final is None else final.to(device), gop)
+    runs = runs.tolist()
+    if not batched:
+        r = runs[0]
+        return Recognition(phonemes[0, :r], starts[0, :r + 1], total[0], score[0, :r], below[0, :r] if gop else None)
+    return Recognition(
+        [phonemes[b, :r] for b, r in enumerate(runs)], [starts[b, :r + 1] for b, r in enumerate(runs)], total,
+        [score[b, :r] for b, r in enumerate(runs)], [below[b, :r] for b, r in enumerate(runs)] if gop else None)
 
 
 def _queries(phonemes):

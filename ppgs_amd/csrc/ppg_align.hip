@@ -1,6 +1,7 @@
 // Forced alignment of a PPG to a phoneme sequence with goodness-of-pronunciation scores, and the free-running
 // run-length decode, on the device.  Phrase search (ppg_search) stands at the end, and after
-// it the same search carried across the pushes of a stream (ppg_search_stream_*).
+// it the same search carried across the pushes of a stream (ppg_search_stream_*), and last the phoneme
+// recogniser, the best path through all 40 phonemes under a transition model (ppg_recognize).
 //
 //   e[t, n] = logf(min(max(P[s[n], t], 1e-8), 1 - 1e-8))                      (the clamp of ppg_distance)
 //   D[0, 0] = e[0, 0];  D[0, n > 0] = -inf
@@ -35,11 +36,12 @@
 //   align_score_optional       align_score for transcripts that may be longer than the utterance.
 //
 // What the kernels share stands once: WALK_FRAMES is the frame loop (staging, double buffering, the gather one frame
-// ahead, the barriers) of the four programmes, each of which hands it its recurrence.  `search_strips` is
+// ahead, the barriers) of the five programmes, each of which hands it its recurrence.  `search_strips` is
 // the one body of both searches, `traceback` of both trace-backs (one or two bit planes), `score_phoneme` of both
-// scores, `refused` their test of an utterance the programme refused, `symbols_fine` the phoneme range check.  The
-// __global__ entries keep their names and are thin where a body is shared.  The host entries share their rungs
-// (check_*, select_device, launched) at the end of the file.
+// scores, `refused` their test of an utterance the programme refused, `symbols_fine` the phoneme range check,
+// `open_runs` the run compression of decode_runs and recognize_runs.  The __global__ entries keep their names and are
+// thin where a body is shared.  The host entries share their rungs (check_*, select_device, launched) at the end of
+// the file.
 #include "../../include/ppgs_amd.h"
 
 #include <hip/hip_runtime.h>
@@ -361,6 +363,23 @@ __global__ __launch_bounds__(64) void align_score(const float* __restrict__ logp
     score_phoneme<false>(logp, frames, lengths, phonemes, max_phonemes, phoneme_lengths, total, starts, score, gop);
 }
 
+// Run compression of 64 frames' labels, lane = frame `t` of them (label -2 at or past T): a frame whose label differs
+// from the frame before it opens a run; the runs' places come from a ballot and a popcount prefix.  `carry` is the
+// label before these frames (-1 before frame 0), `base` the runs so far.  Wave-uniform control flow.
+__device__ __forceinline__ void open_runs(int label, int t, int T, int lane, int& carry, int& base,
+                                          int* out_phonemes, int* out_starts) {
+    const int before = lane_up(label, carry);
+    const bool opens = t < T && label != before;
+    const unsigned long long mask = __ballot(opens);
+    if (opens) {
+        const int at = base + __popcll(mask & ((1ull << lane) - 1ull));
+        out_phonemes[at] = label;
+        out_starts[at] = t;
+    }
+    base += __popcll(mask);
+    carry = __builtin_amdgcn_readlane(label, 63);
+}
+
 // grid (items), 64 threads: lane = frame of the current 64
 __global__ __launch_bounds__(64) void decode_runs(const float* __restrict__ ppg, int frames,
                                                    const int* __restrict__ lengths, int* __restrict__ phonemes,
@@ -388,16 +407,7 @@ __global__ __launch_bounds__(64) void decode_runs(const float* __restrict__ ppg,
                 if (v > best) { best = v; label = p; }         // the lowest index on ties
             }
         }
-        const int before = lane_up(label, carry);
-        const bool opens = t < T && label != before;
-        const unsigned long long mask = __ballot(opens);
-        if (opens) {
-            const int at = base + __popcll(mask & ((1ull << lane) - 1ull));
-            out_phonemes[at] = label;
-            out_starts[at] = t;
-        }
-        base += __popcll(mask);
-        carry = __builtin_amdgcn_readlane(label, 63);
+        open_runs(label, t, T, lane, carry, base, out_phonemes, out_starts);
     }
     if (lane == 0) { runs[item] = base; out_starts[base] = T; }
 }
@@ -926,6 +936,200 @@ __global__ __launch_bounds__(64) void search_stream_reset(int max_phonemes, cons
     }
 }
 
+// ---- phoneme recognition (ppg_recognize) ----
+//
+// What was said: the best path through the 40 phonemes under a transition model A (40, 40), A[p, q] the weight of going
+// from p at frame t-1 to q at frame t, with weights `initial` on the first frame's state and `final` on the last one's.
+//   e[t, q] = the prepared frame of align_prepare
+//   D[0, q] = e[0, q] + initial[q]
+//   c[p]    = D[t-1, p] + A[p, q]                              one fp32 addition per candidate
+//   best = c[q], from = q;  for p = 0 .. 39, p != q:  if c[p] > best: best = c[p], from = p
+//   D[t, q] = e[t, q] + best                                   fp32, in order of t
+//   F[q] = D[T-1, q] + final[q];  last = the first q with the largest F (strict >, ascending q);  total = F[last]
+// Comparisons only: staying beats switching and the lowest predecessor beats a higher one on ties; -inf + finite = -inf
+// and -inf > -inf is false, so a state nothing reaches never gives NaN.  With the left-to-right chain of a transcript
+// as A this is align_programme bit for bit, with A = 0 it is decode_runs.  Three kernels beside align_prepare and
+// align_score, which are shared:
+//   recognize_programme  one wave per utterance, lane q < 40 = state q: D[q] in a register, column A[., q] in 40
+//                        registers, the emission through WALK_FRAMES with S = 1 and the identity as phoneme table.  A
+//                        frame is a 40 x 40 max-plus product: every lane needs all 40 D[p], which come as wave-uniform
+//                        operands from 40 v_readlane_b32 with constant lane index (DESIGN 4.15 has the comparison with
+//                        the broadcast through LDS).  Lanes 40 .. 63 hold -inf and are never a predecessor.  One
+//                        back-pointer byte per state and frame; a lane packs four frames into a dword, so the wave
+//                        stores 256 contiguous bytes every fourth frame.
+//   recognize_traceback  one wave per utterance: back-pointer rows come through LDS 64 frames (4 KiB) at a time, the next
+//                        refill in flight; the walk is wave-uniform; lane t % 64 keeps frame t's label and the wave
+//                        stores 64 labels at once.
+//   recognize_runs       one wave per utterance: decode_runs' run compression (open_runs) on the label row.
+// align_score then scores the runs as a transcript of `runs` phonemes among at most `frames`.
+
+constexpr int BACK = 4;                       // frames per back-pointer dword
+constexpr int BACK_ROW = 64 * BACK;           // bytes a wave stores per BACK frames
+constexpr int BACK_VEC = WALK / BACK * BACK_ROW / 16;          // 16-byte pieces per refill of the trace-back: 256
+
+struct RecognizeLayout {
+    size_t logp, back, labels, ends, bytes;   // byte offsets into the workspace
+};
+
+// back-pointer bytes of one utterance: whole dwords of BACK frames
+__host__ __device__ inline size_t back_bytes(int frames) { return (size_t)((frames + BACK - 1) / BACK) * BACK_ROW; }
+
+// (65535 items of 262144 frames are 4.2e12 bytes: inside a size_t)
+inline RecognizeLayout recognize_layout(int items, int frames) {
+    RecognizeLayout w{};
+    size_t at = 0;
+    w.logp = at; at += prepared_bytes(items, frames);
+    w.back = at; at = align256(at + (size_t)items * back_bytes(frames));
+    w.labels = at; at = align256(at + (size_t)items * frames * sizeof(int));
+    w.ends = at; at = align256(at + (size_t)items * sizeof(int));
+    w.bytes = at;
+    return w;
+}
+
+// lane p's value as a wave-uniform operand
+__device__ __forceinline__ float from_lane(float v, int p) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), p));
+}
+
+// grid (items), 64 threads.  initial and final_ may be null: all zeros.  An utterance whose length is impossible gets
+// total = NaN and runs = 0, one without a path total = -inf and runs = 0; every other its total, its end state in
+// `ends` and its back-pointers.
+__global__ __launch_bounds__(64) void recognize_programme(const float* __restrict__ logp, int frames,
+                                                           const int* __restrict__ lengths,
+                                                           const float* __restrict__ transitions,
+                                                           const float* __restrict__ initial,
+                                                           const float* __restrict__ final_,
+                                                           uint32_t* __restrict__ back, int* __restrict__ ends,
+                                                           int* __restrict__ runs, float* __restrict__ total)
+{
+    __shared__ float4 stage[2][CHUNK_VEC];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item];
+    if (T < 1 || T > frames) {                                 // (uniform)
+        if (lane == 0) { total[item] = NAN; runs[item] = 0; }
+        return;
+    }
+    const bool state = lane < NP;
+    const int s[1] = {state ? lane : 0};                       // the identity; lanes 40 .. 63 run along on phoneme 0
+    float a[NP];                                               // column `lane` of the transitions
+#pragma unroll
+    for (int p = 0; p < NP; ++p) a[p] = state ? transitions[p * NP + lane] : -INFINITY;
+    const float stay = state ? transitions[lane * NP + lane] : -INFINITY;
+    const float first = !state ? -INFINITY : initial ? initial[lane] : 0.f;
+    const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
+    uint32_t* out = back + (size_t)item * (back_bytes(frames) / 4);
+    float d = -INFINITY;
+    uint32_t packed = 0;                                       // this lane's back-pointers of up to BACK frames
+    WALK_FRAMES(1, false, t, cur,
+        int from = lane;
+        if (t == 0) {                                          // (uniform)
+            d = cur[0] + first;
+        } else {
+            const float before = d;
+            float best = before + stay;                        // staying: what a switch has to beat
+            _Pragma("unroll") for (int p0 = 0; p0 < NP; p0 += 8) {
+                float c[8];                                    // eight at a time: the moves stand ahead of their uses
+                _Pragma("unroll") for (int j = 0; j < 8; ++j) c[j] = from_lane(before, p0 + j);
+                _Pragma("unroll") for (int j = 0; j < 8; ++j) c[j] += a[p0 + j];
+                _Pragma("unroll") for (int j = 0; j < 8; ++j) {    // ascending: the lowest of equal predecessors stays
+                    const bool better = c[j] > best;           // (p = lane repeats `best` or less: never taken)
+                    best = better ? c[j] : best;
+                    from = better ? p0 + j : from;
+                }
+            }
+            d = cur[0] + best;                                 // -inf + finite = -inf: never NaN
+        }
+        packed |= (uint32_t)from << (8 * (t % BACK));
+        if (t % BACK == BACK - 1) {                            // (uniform)
+            out[(size_t)(t / BACK) * 64 + lane] = packed;
+            packed = 0;
+        })
+    if (T % BACK) out[(size_t)(T / BACK) * 64 + lane] = packed;            // (uniform) the last, partial dword
+    const float last = d + (!state ? -INFINITY : final_ ? final_[lane] : 0.f);
+    float sum = from_lane(last, 0);
+    int end = 0;
+#pragma unroll
+    for (int q = 1; q < NP; ++q) {                             // wave-uniform: the first of the largest
+        const float f = from_lane(last, q);
+        const bool better = f > sum;
+        sum = better ? f : sum;
+        end = better ? q : end;
+    }
+    if (lane == 0) {
+        total[item] = sum;
+        if (sum > -INFINITY) ends[item] = end;
+        else runs[item] = 0;                                   // no path: nothing else is written
+    }
+}
+
+// whether the programme left a path for this utterance: a plausible length and a total above -inf (NaN is not)
+__device__ __forceinline__ bool recognized(int T, int frames, const float* __restrict__ total) {
+    return T >= 1 && T <= frames && *total > -INFINITY;
+}
+
+// grid (items), 64 threads
+__global__ __launch_bounds__(64) void recognize_traceback(const uint32_t* __restrict__ back, int frames,
+                                                           const int* __restrict__ lengths,
+                                                           const float* __restrict__ total,
+                                                           const int* __restrict__ ends, int* __restrict__ labels)
+{
+    __shared__ uint4 rows[BACK_VEC];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item];
+    if (!recognized(T, frames, total + item)) return;          // (uniform)
+    const uint4* src = reinterpret_cast<const uint4*>(back + (size_t)item * (back_bytes(frames) / 4));
+    int* out = labels + (size_t)item * frames;
+    constexpr int PER = BACK_VEC / 64;
+    uint4 next[PER];
+    auto load = [&](int c) {                                   // rows of frames c * WALK ..., whole dwords below T only
+        const int pieces = (min(WALK, T - c * WALK) + BACK - 1) / BACK * (BACK_ROW / 16);
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int idx = u * 64 + lane;
+            next[u] = idx < pieces ? src[(size_t)c * BACK_VEC + idx] : make_uint4(0, 0, 0, 0);
+        }
+    };
+    int n = min(max(ends[item], 0), NP - 1);
+    int c = (T - 1) / WALK;
+    load(c);
+    for (; c >= 0; --c) {
+        __syncthreads();                                       // the walk over the previous refill is over
+#pragma unroll
+        for (int u = 0; u < PER; ++u) rows[u * 64 + lane] = next[u];
+        __syncthreads();
+        if (c > 0) load(c - 1);
+        const uint8_t* row = reinterpret_cast<const uint8_t*>(rows);
+        const int high = min(T - 1, c * WALK + WALK - 1);
+        int mine = 0;
+        for (int t = high; t >= c * WALK; --t) {
+            if (lane == (t & (WALK - 1))) mine = n;            // frame t's label
+            // frame t's predecessor: the same address in every lane (frame 0 has none; its byte is not used)
+            if (t > 0) n = row[((t & (WALK - 1)) / BACK * 64 + n) * BACK + t % BACK] & 63;
+        }
+        if (c * WALK + lane <= high) out[c * WALK + lane] = mine;
+    }
+}
+
+// grid (items), 64 threads: lane = frame of the current 64
+__global__ __launch_bounds__(64) void recognize_runs(const int* __restrict__ labels, int frames,
+                                                      const int* __restrict__ lengths,
+                                                      const float* __restrict__ total, int* __restrict__ phonemes,
+                                                      int* __restrict__ starts, int* __restrict__ runs)
+{
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item];
+    if (!recognized(T, frames, total + item)) return;          // (uniform) the programme has set runs = 0
+    const int* src = labels + (size_t)item * frames;
+    int* out_phonemes = phonemes + (size_t)item * frames;
+    int* out_starts = starts + (size_t)item * (frames + 1);
+    int carry = -1, base = 0;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        open_runs(t < T ? src[t] : -2, t, T, lane, carry, base, out_phonemes, out_starts);
+    }
+    if (lane == 0) { runs[item] = base; out_starts[base] = T; }
+}
+
 // ---- the rungs the host entries share, in the order every entry takes them.  Each returns PPG_OK or has left its
 // message; nothing is launched before the last of an entry's checks has passed. ----
 
@@ -1063,6 +1267,41 @@ int ppg_decode(int device, const float* ppg, int frames, int items, const int32_
     hipLaunchKernelGGL(decode_runs, dim3(items), dim3(64), 0, static_cast<hipStream_t>(stream), ppg, frames, lengths,
                        phonemes, starts, runs);
     return launched("decode");
+}
+
+size_t ppg_recognize_workspace_bytes(int items, int frames) {
+    if (items <= 0 || items > PPG_RECOGNIZE_MAX_ITEMS || frames <= 0 || frames > PPG_RECOGNIZE_MAX_FRAMES) return 0;
+    return recognize_layout(items, frames).bytes;
+}
+
+int ppg_recognize(int device, const float* ppg, int frames, int items, const int32_t* lengths,
+                  const float* transitions, const float* initial, const float* final_, int32_t* phonemes,
+                  int32_t* starts, int32_t* runs, float* total, float* score, float* gop, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+    if (const int rc = check_common("recognize", ppg, frames, items, lengths, PPG_RECOGNIZE_MAX_FRAMES,
+                                    PPG_RECOGNIZE_MAX_ITEMS))
+        return rc;
+    if (!transitions || !phonemes || !starts || !runs || !total || !score || !workspace)
+        return ppg::fail_message(PPG_EINVAL, "recognize: bad argument");
+    const RecognizeLayout w = recognize_layout(items, frames);
+    if (const int rc = check_workspace("recognize", workspace, workspace_bytes, w.bytes)) return rc;
+    if (const int rc = select_device(device)) return rc;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    float* logp = reinterpret_cast<float*>(ws + w.logp);
+    uint32_t* back = reinterpret_cast<uint32_t*>(ws + w.back);
+    int* labels = reinterpret_cast<int*>(ws + w.labels);
+    int* ends = reinterpret_cast<int*>(ws + w.ends);
+    hipLaunchKernelGGL(align_prepare, dim3((frames + 63) / 64, items), dim3(64), 0, s, ppg, frames, lengths, logp);
+    hipLaunchKernelGGL(recognize_programme, dim3(items), dim3(64), 0, s, logp, frames, lengths, transitions, initial,
+                       final_, back, ends, runs, total);
+    hipLaunchKernelGGL(recognize_traceback, dim3(items), dim3(64), 0, s, back, frames, lengths, total, ends, labels);
+    hipLaunchKernelGGL(recognize_runs, dim3(items), dim3(64), 0, s, labels, frames, lengths, total, phonemes, starts,
+                       runs);
+    // the runs as a transcript: at most `frames` phonemes, `runs` of them
+    hipLaunchKernelGGL(align_score, dim3((frames + 63) / 64, items), dim3(64), 0, s, logp, frames, lengths, phonemes,
+                       frames, runs, total, starts, score, gop);
+    return launched("recognize");
 }
 
 size_t ppg_search_workspace_bytes(int items, int frames, int queries) {

@@ -162,6 +162,11 @@ SYMBOLS = {
     'ppg_decode': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_recognize_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    'ppg_recognize': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'ppg_search_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'ppg_search': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
@@ -731,15 +736,15 @@ ALIGN_MAX_ITEMS = 65535          # PPG_ALIGN_MAX_ITEMS, per call of the library
 ALIGN_WORKSPACE_BYTES = 1 << 30  # a larger batch runs as several calls, each within this much workspace
 
 
-def _items(ppg, lengths, what):
-    """The checks and conversions align_items and decode_items share: (x, lengths on the device as int32)."""
+def _items(ppg, lengths, what, most=ALIGN_MAX_FRAMES):
+    """The checks and conversions align_items, decode_items and recognize_items share: (x, lengths as host integers)."""
     if not ppg.is_cuda:
         raise PpgError('ppgs_amd: the post-ops work on HIP device tensors')
     x = ppg.to(torch.float32).contiguous()
     if x.dim() != 3 or x.shape[1] != 40 or x.shape[0] < 1:
         raise ValueError(f'PPGs must be (items >= 1, 40, frames), got {tuple(x.shape)}')
-    if not 1 <= x.shape[2] <= ALIGN_MAX_FRAMES:
-        raise ValueError(f'{what} takes 1 to {ALIGN_MAX_FRAMES} frames, got {x.shape[2]}')
+    if not 1 <= x.shape[2] <= most:
+        raise ValueError(f'{what} takes 1 to {most} frames, got {x.shape[2]}')
     lengths = [int(v) for v in lengths]
     if len(lengths) != x.shape[0]:
         raise ValueError(f'{len(lengths)} lengths for {x.shape[0]} items')
@@ -814,6 +819,56 @@ def decode_items(ppg, lengths):
                 device.index, x[at:].data_ptr(), frames, min(ALIGN_MAX_ITEMS, items - at), lengths[at:].data_ptr(),
                 phonemes[at:].data_ptr(), starts[at:].data_ptr(), runs[at:].data_ptr(), stream))
     return phonemes, starts, runs
+
+
+RECOGNIZE_MAX_FRAMES = 262144    # PPG_RECOGNIZE_MAX_FRAMES
+RECOGNIZE_MAX_ITEMS = 65535      # PPG_RECOGNIZE_MAX_ITEMS, per call of the library
+RECOGNIZE_WORKSPACE_BYTES = 1 << 30  # a larger batch runs as several calls, each within this much workspace
+
+
+def recognize_items(ppg, lengths, transitions, initial=None, final=None, want_gop=True):
+    """Phoneme recognition of item b = ppg[b, :, :lengths[b]] (ppg_recognize): the best path through the 40 phonemes
+    under `transitions` (40, 40) fp32, `initial` and `final` (40,) fp32 or None for zeros, all on the device of `ppg`
+    and every entry finite or -inf (the caller's to check).  (items, 40, frames) on a GPU, lengths as host integers ->
+    phonemes (items, frames) int32, starts (items, frames + 1) int32, runs (items,) int32, total (items,) fp32, score
+    and gop (items, frames) fp32 (gop None without want_gop).  Entries past an item's runs (runs + 1 for starts) are
+    zero; an item without a path has runs = 0 and total = -inf."""
+    x, lengths = _items(ppg, lengths, 'recognize', RECOGNIZE_MAX_FRAMES)
+    items, frames = x.shape[0], x.shape[2]
+    device = x.device
+
+    def weights(tensor, shape, name):
+        if tensor is None:
+            return None
+        if not torch.is_tensor(tensor) or tuple(tensor.shape) != shape:
+            raise ValueError(f'{name} must be a {shape} tensor, got {tuple(getattr(tensor, "shape", ()))}')
+        return tensor.to(device=device, dtype=torch.float32).contiguous()
+    transitions = weights(transitions, (40, 40), 'transitions')
+    if transitions is None:
+        raise ValueError('recognize takes a (40, 40) tensor of transitions')
+    initial, final = weights(initial, (40,), 'initial'), weights(final, (40,), 'final')
+    lengths = torch.tensor(lengths, dtype=torch.int32).to(device)
+    phonemes = torch.zeros((items, frames), dtype=torch.int32, device=device)
+    starts = torch.zeros((items, frames + 1), dtype=torch.int32, device=device)
+    runs = torch.empty((items,), dtype=torch.int32, device=device)
+    total = torch.empty((items,), dtype=torch.float32, device=device)
+    score = torch.zeros((items, frames), dtype=torch.float32, device=device)
+    gop = torch.zeros((items, frames), dtype=torch.float32, device=device) if want_gop else None
+    lib = library()
+    bytes_for = lib.ppg_recognize_workspace_bytes
+    group = max(1, min(items, RECOGNIZE_MAX_ITEMS, RECOGNIZE_WORKSPACE_BYTES // bytes_for(1, frames)))
+    size = bytes_for(group, frames)
+    workspace = torch.empty((size,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for at in range(0, items, group):
+            _check(lib.ppg_recognize(
+                device.index, x[at:].data_ptr(), frames, min(group, items - at), lengths[at:].data_ptr(),
+                transitions.data_ptr(), None if initial is None else initial.data_ptr(),
+                None if final is None else final.data_ptr(), phonemes[at:].data_ptr(), starts[at:].data_ptr(),
+                runs[at:].data_ptr(), total[at:].data_ptr(), score[at:].data_ptr(),
+                gop[at:].data_ptr() if want_gop else None, workspace.data_ptr(), size, stream))
+    return phonemes, starts, runs, total, score, gop
 
 
 SEARCH_MAX_FRAMES = 262144       # PPG_SEARCH_MAX_FRAMES
