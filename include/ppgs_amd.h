@@ -763,6 +763,86 @@ int ppg_search_stream_flush(int device, void* state, int streams, int queries, i
                             int32_t* begin, int32_t* end, float* total, float* mean, int32_t* count, void* stream);
 
 /*
+ * Live phoneme recognition: ppg_recognize carried across the pushes of a stream (captions, a pronunciation tutor, an
+ * endpointer on a live PPG).  A push does work proportional to its own frames and to the frames whose label can still
+ * change, whatever the age of the stream, and gives out the runs that have become final.  Not in the reference.
+ *
+ * One stream has a position p, the frames received since its last reset (frame indices are absolute: they count from the
+ * reset); a commit point c, 0 <= c <= p: frames below c have had their label given out for good; D[0 .. 39] of frame
+ * p-1; a ring of `window` = W frames that holds the back-pointers, the prepared frames (the 40 log-posteriors and their
+ * maximum, as ppg_align prepares them) and the labels of the frames in [c, p); one open run (label, start frame, fp32
+ * sum and below); a counter `forced`; and, as a short cut, every state's ancestor path(q, c), carried forward frame by
+ * frame: where the alive states' ancestors differ a push can commit nothing unless by force, and no path is walked.
+ *   Forward.  ppg_recognize's recurrence, unchanged: the same prepared frame, D[0, q] = e[0, q] + initial[q] at absolute
+ *   frame 0, one fp32 addition per candidate, staying first, then ascending p with strict >, D[t, q] = e[t, q] + best.
+ *   For any split of a recording into pushes, D and the back-pointers of every frame are the bits ppg_recognize computes
+ *   for the whole recording (one body of code).
+ *   Commit, once per stream and push, after the push's frames, with t = p-1.  alive(q) means D[q] > -inf; path(q, u) is
+ *   the state at frame u of the trace-back from q at t.
+ *     1. Natural.  v = the largest u in [c, t] at which path(q, u) is the same for every alive q; if there is none,
+ *        v = c-1.  Frames c .. v get that path's labels and c = v+1.  If no state is alive nothing is committed, now or
+ *        later.  Whatever comes later, the best path ends in a state that is alive now, so these labels are final; c
+ *        after a push depends only on the frames received so far, not on how they were split.
+ *     2. Forced (max_lag = L, 0 <= L < W), only if p - c > L after step 1.  best = the first alive q with the largest
+ *        D[q] (strict >, ascending, no `final`).  Frames c .. p-L-1 get path(best, .); with g = path(best, p-L-1), every q
+ *        with path(q, p-L-1) != g gets D[q] = -inf, so the later path stays consistent with what was given out; `forced`
+ *        grows by the number of frames committed this way and c = p-L.  A forced commit depends on where pushes end.
+ *     3. Runs.  Each newly committed frame, in order, either extends the open run (sum += e[t, label], below +=
+ *        e[t, label] - max[t], fp32, from 0.f: the order of ppg_align's score) or closes it and opens a new one.  A
+ *        closed run is emitted as (phoneme, begin, end, sum / float(end - begin), below / float(end - begin)).
+ *   A stream with (p - c) + lengths[i] > W is an impossible item: count = -1 and its state stays untouched; so is a
+ *   length outside [0, frames] and a position that would pass INT32_MAX.  The check is made on the device.
+ *   flush: F[q] = D[q] + final[q]; last = the first q with the largest F; total = F[last].  If total > -inf, everything
+ *   up to p is committed along path(last, .).  The open run is closed and emitted, total and forced are reported, and
+ *   the stream is reset: a flush ends an utterance.  reset puts p = c = 0, every D to -inf, no open run, forced = 0.
+ *   If forced == 0 and ppg_recognize finds a path, the runs of all pushes and of the flush, concatenated, are
+ *   ppg_recognize's phonemes, starts, score and gop of the whole recording and flush's total is its total, bit for bit,
+ *   for every split, pushes of 0 and 1 frames included.
+ *
+ * The caller owns the state (device memory, 16-byte aligned, ppg_recognize_stream_state_bytes(streams, window) bytes, to
+ * be reset before its first push); there is no handle.  Six blocks, each 256-byte aligned: the head of every stream (8
+ * words: p, c, forced, the open run's label or -1, its start, sum, below, 1 spare), D of every stream (64 words: a whole
+ * wave, lanes 40 .. 63 at -inf), the ancestors of every stream (64 words, int32), the back-pointer rings (64 B per frame: one byte per state, in dwords of four frames),
+ * the rings of prepared frames (176 B per frame) and the rings of labels (int32).  Frame t lives in slot t % W.
+ *
+ * ppg_recognize_stream_push: every stream takes lengths[i] frames.
+ *   ppg          : device fp32 (streams, 40, frames), padded; frames at or past a stream's length are never read
+ *   lengths      : device int32[streams], each in [0, frames]; a stream with 0 sits out the step (its commit runs)
+ *   transitions  : device fp32 (40, 40); initial: device fp32[40] or NULL for zeros (used at absolute frame 0 only)
+ *   max_lag, cap : 0 <= max_lag < window; cap >= 1 is the number of run slots per stream
+ *   phonemes, begin, end : device int32 (streams, cap);  score, gop : device fp32 (streams, cap), gop may be NULL
+ *   count        : device int32[streams]: the runs closed in this push.  Only the first min(count, cap) are written, so
+ *                  count > cap says that the push overflowed (as snprintf does); slots at or past count are -1 / NaN.  A
+ *                  push closes at most (p - c) + lengths[i] runs.  An impossible item gets count = -1 and nothing else.
+ *   workspace    : device memory, 16-byte aligned, at least ppg_recognize_stream_workspace_bytes(streams, frames) bytes:
+ *                  the prepared frames of this push
+ * ppg_recognize_stream_flush: final_ is device fp32[40] or NULL for zeros; the run outputs as above, (streams, cap), at
+ * most (p - c) + 1 runs; total fp32[streams], forced int32[streams].  ppg_recognize_stream_reset and _flush take `which`,
+ * device int32[streams] flags of the streams meant, or NULL for all; the other streams keep their state, and flush gives
+ * them count = 0, total = NaN and forced = -1.
+ * Kernel launches on `stream` only: no allocation, synchronisation or copy.  Every byte a kernel reads was written by
+ * reset or by an earlier kernel of the same stream of calls.  Every stream's results are a function of that stream alone.
+ * PPG_EINVAL, and nothing launched, for: more than PPG_RECOGNIZE_STREAM_MAX_STREAMS streams, a window that is not a
+ * multiple of 64 in [PPG_RECOGNIZE_STREAM_MIN_WINDOW, PPG_RECOGNIZE_STREAM_MAX_WINDOW], frames outside
+ * 1 .. PPG_RECOGNIZE_MAX_FRAMES, max_lag outside [0, window), cap < 1, a NULL or unaligned (16 bytes for the state and the
+ * workspace, 4 for the others) state, workspace, input or output, a short workspace.  The two *_bytes helpers are
+ * host-only and return 0 for impossible arguments.
+ */
+#define PPG_RECOGNIZE_STREAM_MIN_WINDOW 64
+#define PPG_RECOGNIZE_STREAM_MAX_WINDOW 65536
+#define PPG_RECOGNIZE_STREAM_MAX_STREAMS 65535
+size_t ppg_recognize_stream_state_bytes(int streams, int window);
+size_t ppg_recognize_stream_workspace_bytes(int streams, int frames);
+int ppg_recognize_stream_reset(int device, void* state, int streams, int window, const int32_t* which, void* stream);
+int ppg_recognize_stream_push(int device, void* state, int streams, int window, const float* ppg, int frames,
+                              const int32_t* lengths, const float* transitions, const float* initial, int max_lag,
+                              int cap, int32_t* phonemes, int32_t* begin, int32_t* end, float* score, float* gop,
+                              int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+int ppg_recognize_stream_flush(int device, void* state, int streams, int window, const float* final_,
+                               const int32_t* which, int cap, int32_t* phonemes, int32_t* begin, int32_t* end,
+                               float* score, float* gop, int32_t* count, float* total, int32_t* forced, void* stream);
+
+/*
  * Frame metrics accumulated on the device: what the reference's `python -m ppgs.evaluate` computes per batch with
  * five metric objects (ppgs/evaluate/metrics.py: Accuracy, CategoricalAccuracy, JensenShannon, TopKAccuracy, Loss,
  * DistanceMatrix), here ONE kernel launch per batch into one device block, no host synchronisation, read once at

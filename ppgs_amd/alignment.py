@@ -90,6 +90,46 @@ bit whatever the push sizes, with an online rule that gives a hit out once nothi
     spotter = ppgs_amd.alignment.SearchStream(['hh', 'ah', 'l', 'ow'], threshold=-1., patience=25)
     hits = spotter.push(frames)          # (40, k) as a stream emits them, k >= 0; Hits of this push
     last = spotter.flush()
+
+Live phoneme recognition (`RecognizeStream`, ppg_recognize_stream_*): `recognize` carried across the pushes of a stream.
+One stream has a position p, the frames received since the last reset (frame indices are absolute); a commit point c,
+0 <= c <= p: frames below c have had their label given out for good; D[0 .. 39] of frame p-1; a ring of `window` = W
+frames that holds the back-pointers and the prepared frames (the 40 log-posteriors and their maximum) of the frames in
+[c, p); one open run (label, start frame, fp32 sum and below); and a counter `forced`.
+
+    Forward.  The recurrence of `recognize`, unchanged: the same prepared frame, D[0, q] = e[0, q] + initial[q] at
+    absolute frame 0, one fp32 addition per candidate, staying first, then ascending p with strict >, D[t, q] =
+    e[t, q] + best.  For any split of a recording into pushes, D and the back-pointers of every frame are the bits
+    `recognize` computes for the whole recording: it is one body of code.
+    Commit, once per stream and push, after the push's frames, with t = p-1.  alive(q) means D[q] > -inf; path(q, u)
+    is the state at frame u of the trace-back from q at t.
+      1. Natural.  v = the largest u in [c, t] at which path(q, u) is the same for every alive q; if there is none,
+         v = c-1.  Frames c .. v get that path's labels and c = v+1.  If no state is alive nothing is committed, now or
+         later.  Whatever comes later, the best path ends in a state that is alive now, so these labels are final; c
+         after a push depends only on the frames received so far, not on how they were split.
+      2. Forced (max_lag = L, 0 <= L < W), only if p - c > L after step 1.  best = the first alive q with the largest
+         D[q] (strict >, ascending, no `final`).  Frames c .. p-L-1 get path(best, .); with g = path(best, p-L-1),
+         every q with path(q, p-L-1) != g gets D[q] = -inf, so the later path stays consistent with what was given
+         out; `forced` grows by the number of frames committed this way and c = p-L.  A forced commit depends on
+         where pushes end; natural commits do not.
+      3. Runs.  Each newly committed frame, in order, either extends the open run (sum += e[t, label], below +=
+         e[t, label] - max[t], fp32, from 0.f: the order of `forced`'s score) or closes it and opens a new one.  A
+         closed run is emitted as (phoneme, begin, end, sum / float(end - begin), below / float(end - begin)).
+    A stream with (p - c) + its frames > W cannot take them: count = -1 and its state stays untouched (the check is
+    made on the device; the host does not know c).  flush(final): F[q] = D[q] + final[q]; last = the first q with the
+    largest F; total = F[last]; if total > -inf everything up to p is committed along path(last, .); the open run is
+    closed and emitted, total and forced are reported, and the stream is reset: a flush ends an utterance.  reset puts
+    p = c = 0, every D to -inf, no open run and forced = 0.
+    If forced == 0 and `recognize` finds a path, the runs of all pushes and of the flush, concatenated, are
+    `recognize(recording, ...)`'s phonemes, starts, score and gop, and flush's total is its total, bit for bit, for every
+    split, pushes of 0 and 1 frames included.
+Not here: a provisional hypothesis for the uncommitted tail, N-best lists, a matrix per stream, state spaces beyond the
+40 phonemes.
+
+    said = ppgs_amd.alignment.RecognizeStream(penalty=4.)
+    runs = said.push(frames)             # (40, k) as a stream emits them, k >= 0; Runs this push has made final
+    for name, start, end, score, gop in ppgs_amd.alignment.run_segments(runs): ...
+    last = said.flush()                  # the rest, with total and forced; the stream starts again at frame 0
 """
 import collections
 import math
@@ -110,6 +150,7 @@ Alignment = collections.namedtuple('Alignment', ['phonemes', 'starts', 'total', 
 Decoding = collections.namedtuple('Decoding', ['phonemes', 'starts'])
 Recognition = collections.namedtuple('Recognition', Alignment._fields)
 Hits = collections.namedtuple('Hits', ['phonemes', 'begin', 'end', 'total', 'mean', 'count', 'curve'])
+Runs = collections.namedtuple('Runs', ['phonemes', 'begin', 'end', 'score', 'gop', 'count', 'total', 'forced'])
 
 
 def _ppg(ppg, most=MAX_FRAMES, what='alignment'):
@@ -711,6 +752,208 @@ class SearchStream:
         self._ensure()
         engine.search_stream_reset(self._state, self._streams, len(self._counts), self._most, which)
         self._position = [0 if item is None or b == item else position for b, position in enumerate(self._position)]
+
+
+class RecognizeStream:
+    """`recognize` on a live stream: the frames come a few at a time, the Viterbi decode is carried across the pushes on
+    the device, and runs of phonemes come out as soon as they are final (see the module's text for the definition).
+
+        said = ppgs_amd.alignment.RecognizeStream(penalty=4.)
+        for piece in pieces:                                     # each (40, k), k >= 0
+            for name, start, end, score, gop in ppgs_amd.alignment.run_segments(said.push(piece)): ...
+        last = said.flush()
+
+    Exactly one of `transitions` (40, 40) and `penalty` is given, `initial` and `final` (40,) are optional, all checked
+    as `recognize` checks them.  `window` is the ring of every stream in frames, a multiple of 64 from 64 to 65536;
+    `max_lag` (None: window // 2) in [0, window) is the number of frames a label may stay open before it is given out
+    by force.  As long as nothing is forced (`forced` == 0 at the flush) the runs of all pushes and of the flush are
+    `recognize` of the whole recording bit for bit.
+
+    `batch=None` is one stream: push((40, F)).  `batch=B` is B streams side by side: push((B, 40, Fmax), lengths),
+    lengths[b] in [0, Fmax] (None: Fmax each); the padding is never read.  push returns `Runs(phonemes, begin, end,
+    score, gop, count, total, forced)`: phonemes, begin, end (int32), score and gop (fp32; gop None with gop=False) are
+    padded device tensors (cap,) or (B, cap) with cap = max_lag + F, never less than the runs a push can close; count,
+    0-d or (B,), is the number closed in this push; slots at or past it are -1 / NaN; total and forced are None.  A
+    stream that could not take its frames has count = -1.  A push longer than window - max_lag is fed in pieces of
+    that size whose runs are packed behind one another on the device.  A push of no frames (F = 0) returns empty
+    tensors and calls nothing.  flush(item=None) commits the rest along the best path under `final`, closes the open
+    run and resets every stream, or stream `item`: Runs with cap = max_lag + 1 and total (fp32) and forced (int32),
+    0-d or (B,); streams it leaves out have count = 0, total = NaN and forced = -1.  reset(item=None) starts every
+    stream, or that one, again at frame 0.  `position` is the host list of the frames each stream has received.
+    Nothing here waits for the device; the state, the weights and a workspace that only grows belong to the object and
+    live on `device` (None: the device of the first push's tensor, else the current one)."""
+
+    def __init__(self, transitions=None, penalty=None, initial=None, final=None, max_lag=None, window=1024, batch=None,
+                 gop=True, device=None):
+        if (transitions is None) == (penalty is None):
+            raise ValueError('RecognizeStream takes either transitions or penalty: one of them, not both')
+        if transitions is None:
+            transitions = switch_penalty(penalty)
+        count = len(PHONEMES)
+        self._host = (_weights(transitions, (count, count), 'transitions').cpu().contiguous(),
+                      None if initial is None else _weights(initial, (count,), 'initial').cpu().contiguous(),
+                      None if final is None else _weights(final, (count,), 'final').cpu().contiguous())
+        if (isinstance(window, bool) or not isinstance(window, int) or window % 64 or
+                not engine.RECOGNIZE_STREAM_MIN_WINDOW <= window <= engine.RECOGNIZE_STREAM_MAX_WINDOW):
+            raise ValueError(f'window must be a multiple of 64 from {engine.RECOGNIZE_STREAM_MIN_WINDOW} to '
+                             f'{engine.RECOGNIZE_STREAM_MAX_WINDOW} frames, got {window!r}')
+        max_lag = window // 2 if max_lag is None else max_lag
+        if isinstance(max_lag, bool) or not isinstance(max_lag, int) or not 0 <= max_lag < window:
+            raise ValueError(f'max_lag must be a number of frames from 0 to window - 1 = {window - 1}, got {max_lag!r}')
+        if batch is not None and (isinstance(batch, bool) or not isinstance(batch, int) or
+                                  not 1 <= batch <= engine.RECOGNIZE_STREAM_MAX_STREAMS):
+            raise ValueError(f'batch must be None or 1 to {engine.RECOGNIZE_STREAM_MAX_STREAMS} streams, got {batch!r}')
+        self.window, self.max_lag, self.batch, self.gop = window, max_lag, batch, bool(gop)
+        self._streams = 1 if batch is None else batch
+        self._gpu = device
+        self._position = [0] * self._streams
+        self._state = self._workspace = self._weights = None
+        self._uniform, self._flags = {}, {}
+
+    @property
+    def position(self):
+        return list(self._position)
+
+    def _ensure(self, tensor=None):
+        """The device side, made at the first call that needs it."""
+        if self._state is None:
+            device = core.device_for(self._gpu, tensor)
+            self._weights = tuple(None if value is None else value.to(device) for value in self._host)
+            with torch.cuda.device(device):
+                self._state = engine.recognize_stream_state(device, self._streams, self.window)
+        return self._state.device
+
+    def _runs(self, phonemes, begin, end, score, gop, count, total=None, forced=None):
+        def drop(tensor):
+            return tensor if tensor is None or self.batch is not None else tensor[0]
+        return Runs(*[drop(tensor) for tensor in (phonemes, begin, end, score, gop, count, total, forced)])
+
+    def _which(self, item):
+        """The flags of `item` for flush and reset: None for every stream."""
+        if item is None:
+            return None
+        if isinstance(item, bool) or not isinstance(item, int) or not 0 <= item < self._streams:
+            raise ValueError(f'item must be None or a stream index below {self._streams}, got {item!r}')
+        device = self._ensure()
+        if item not in self._flags:
+            self._flags[item] = torch.tensor([int(b == item) for b in range(self._streams)], dtype=torch.int32).to(device)
+        return self._flags[item]
+
+    def push(self, ppg, lengths=None):
+        if not torch.is_tensor(ppg) or ppg.dim() != (2 if self.batch is None else 3):
+            raise ValueError(f'a push takes {"(40, frames)" if self.batch is None else f"({self.batch}, 40, frames)"}, '
+                             f'got {tuple(getattr(ppg, "shape", ()))}')
+        if ppg.shape[-2] != config.OUTPUT_CHANNELS:
+            raise ValueError(f'PPG must have {config.OUTPUT_CHANNELS} channels, got {tuple(ppg.shape)}')
+        if self.batch is not None and ppg.shape[0] != self.batch:
+            raise ValueError(f'a push takes {self.batch} streams, got {ppg.shape[0]}')
+        frames = ppg.shape[-1]
+        if lengths is None:
+            own = [frames] * self._streams
+        else:
+            if self.batch is None:
+                raise ValueError('lengths go with a batch of streams: slice a single PPG instead')
+            if torch.is_tensor(lengths):
+                lengths = lengths.detach().cpu().reshape(-1).tolist()
+            own = [int(value) for value in (lengths if isinstance(lengths, (list, tuple)) else [lengths])]
+            if len(own) != self._streams:
+                raise ValueError(f'lengths has {len(own)} entries for {self._streams} streams')
+            for value in own:
+                if not 0 <= value <= frames:
+                    raise ValueError(f'lengths: {value} is outside [0, {frames}]')
+        for position, value in zip(self._position, own):
+            if position + value > 2 ** 31 - 1:
+                raise ValueError(f'a stream takes at most {2 ** 31 - 1} frames between resets, got {position} + {value}')
+        device = self._ensure(ppg)
+        cap = self.max_lag + frames
+        if frames == 0:
+            def empty(dtype):
+                return torch.empty((self._streams, 0), dtype=dtype, device=device)
+            return self._runs(empty(torch.int32), empty(torch.int32), empty(torch.int32), empty(torch.float32),
+                              empty(torch.float32) if self.gop else None,
+                              torch.zeros((self._streams,), dtype=torch.int32, device=device))
+        x = ppg.to(device=device, dtype=torch.float32)
+        x = x if self.batch is not None else x[None]
+        piece = self.window - self.max_lag                               # what a stream at its full lag can still take
+        whole = None
+        if lengths is not None:                                          # through pinned memory: the copy does not wait
+            whole = torch.tensor(own, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
+        need = engine.library().ppg_recognize_stream_workspace_bytes(self._streams, min(frames, piece))
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty((need,), dtype=torch.uint8, device=device)
+        transitions, initial, _ = self._weights
+        packed = None
+        for at in range(0, frames, piece):
+            size = min(piece, frames - at)
+            if whole is None:
+                if size not in self._uniform:
+                    if len(self._uniform) >= 64:                         # (a stream pushes a few sizes over and over)
+                        self._uniform.clear()
+                    self._uniform[size] = torch.full((self._streams,), size, dtype=torch.int32, device=device)
+                on_device = self._uniform[size]
+            else:
+                on_device = (whole - at).clamp_(0, size)
+            part = engine.recognize_stream_push(
+                self._state, self.window, x[:, :, at:at + size].contiguous(), on_device, transitions, initial,
+                self.max_lag, cap if frames <= piece else self.max_lag + size, self._workspace, self.gop)
+            if frames <= piece:
+                packed = part
+                break
+            packed = self._pack(packed, part, cap)
+        if frames > piece:                                               # without the slot that took what was past count
+            packed = tuple(None if tensor is None else tensor[:, :cap] for tensor in packed[:5]) + (packed[5],)
+        self._position = [position + value for position, value in zip(self._position, own)]
+        return self._runs(*packed)
+
+    def _pack(self, packed, part, cap):
+        """The runs of a piece behind those of the pieces before it, on the device: the counts add up (-1 stays)."""
+        count = part[5]
+        if packed is None:
+            device = count.device
+            packed = tuple(
+                None if tensor is None else torch.full(
+                    (self._streams, cap + 1), math.nan if tensor.is_floating_point() else -1, dtype=tensor.dtype,
+                    device=device) for tensor in part[:5]) + (torch.zeros_like(count),)
+        slots = torch.arange(part[0].shape[1], device=count.device)[None, :]
+        fits = (slots < count[:, None]) & (packed[5][:, None] >= 0)
+        where = torch.where(fits, (packed[5][:, None] + slots).clamp_(max=cap), cap).to(torch.int64)
+        for into, tensor in zip(packed[:5], part[:5]):
+            if tensor is not None:
+                into.scatter_(1, where, tensor)
+                into[:, cap] = math.nan if tensor.is_floating_point() else -1
+        total = torch.where((packed[5] < 0) | (count < 0), torch.full_like(count, -1), packed[5] + count)
+        return packed[:5] + (total,)
+
+    def flush(self, item=None):
+        which = self._which(item)
+        self._ensure()
+        out = engine.recognize_stream_flush(self._state, self._streams, self.window, self._weights[2], self.max_lag + 1,
+                                            which, self.gop)
+        self._position = [0 if item is None or b == item else position for b, position in enumerate(self._position)]
+        return self._runs(*out)
+
+    def reset(self, item=None):
+        which = self._which(item)
+        self._ensure()
+        engine.recognize_stream_reset(self._state, self._streams, self.window, which)
+        self._position = [0 if item is None or b == item else position for b, position in enumerate(self._position)]
+
+
+def run_segments(runs, sample_rate=config.SAMPLE_RATE, hopsize=config.HOPSIZE):
+    """The runs of a push or a flush as a host list of (phoneme name, start seconds, end seconds, score, gop), the first
+    `count` of them, in stream order (gop None if the stream keeps none); a batch of streams gives a list of such
+    lists.  Host only: this is where the results are read."""
+    phonemes, begin, end = runs.phonemes.tolist(), runs.begin.tolist(), runs.end.tolist()
+    score, count = runs.score.tolist(), runs.count.tolist()
+    gop = None if runs.gop is None else runs.gop.tolist()
+
+    def walk(phonemes, begin, end, score, gop, count):
+        return [(PHONEMES[phonemes[r]], begin[r] * hopsize / sample_rate, end[r] * hopsize / sample_rate, score[r],
+                 None if gop is None else gop[r]) for r in range(min(max(count, 0), len(phonemes)))]
+    if isinstance(count, list):
+        return [walk(phonemes[b], begin[b], end[b], score[b], None if gop is None else gop[b], count[b])
+                for b in range(len(count))]
+    return walk(phonemes, begin, end, score, gop, count)
 
 
 def hit_segments(hits, sample_rate=config.SAMPLE_RATE, hopsize=config.HOPSIZE):

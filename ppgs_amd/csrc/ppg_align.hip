@@ -1,7 +1,8 @@
 // Forced alignment of a PPG to a phoneme sequence with goodness-of-pronunciation scores, and the free-running
 // run-length decode, on the device.  Phrase search (ppg_search) stands at the end, and after
-// it the same search carried across the pushes of a stream (ppg_search_stream_*), and last the phoneme
-// recogniser, the best path through all 40 phonemes under a transition model (ppg_recognize).
+// it the same search carried across the pushes of a stream (ppg_search_stream_*), then the phoneme
+// recogniser, the best path through all 40 phonemes under a transition model (ppg_recognize), and last
+// that recogniser carried across the pushes of a stream (ppg_recognize_stream_*).
 //
 //   e[t, n] = logf(min(max(P[s[n], t], 1e-8), 1 - 1e-8))                      (the clamp of ppg_distance)
 //   D[0, 0] = e[0, 0];  D[0, n > 0] = -inf
@@ -37,7 +38,8 @@
 //
 // What the kernels share stands once: WALK_FRAMES is the frame loop (staging, double buffering, the gather one frame
 // ahead, the barriers) of the five programmes, each of which hands it its recurrence.  `search_strips` is
-// the one body of both searches, `traceback` of both trace-backs (one or two bit planes), `score_phoneme` of both
+// the one body of both searches, `recognize_frames` of both recognisers, `traceback` of both trace-backs (one or two
+// bit planes), `score_phoneme` of both
 // scores, `refused` their test of an utterance the programme refused, `symbols_fine` the phoneme range check,
 // `open_runs` the run compression of decode_runs and recognize_runs.  The __global__ entries keep their names and are
 // thin where a body is shared.  The host entries share their rungs (check_*, select_device, launched) at the end of
@@ -48,6 +50,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <initializer_list>
 
 namespace ppg {
 int fail_message(int code, const char* fmt, ...);
@@ -991,6 +994,95 @@ __device__ __forceinline__ float from_lane(float v, int p) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), p));
 }
 
+// What a push of a live recogniser carries into the frames of one stream and out of it again.
+struct Ring {
+    float* d;                                 // D of the stream's last frame: a whole wave's lanes, 40 .. 63 at -inf
+    int base, window;                         // the stream's position; the frames of its ring
+    int* anc; int commit;                     // anc[q] = path(q, c), carried forward; the commit point c
+};
+
+// The frames of one utterance, lane q < 40 = state q: D of the last frame is returned.  Live: one push of T frames of a
+// stream: D comes from `live` and goes back there, frames count from the stream's position (only absolute frame 0
+// takes `initial`), and `out` is the stream's ring of back-pointer dwords, W / BACK rows of 64, where the row of the
+// frames at(t) / BACK wraps; a row the push before left partly filled is taken up again; every state's ancestor at the
+// commit point goes along (what lets the commit skip a walk that cannot commit).  Otherwise `live` is
+// unused:
+// D starts at -inf, frames count from 0 and `out` holds the utterance's rows one after the other.  One body, so the
+// pushes of a stream give D and the back-pointers of the whole recording bit for bit.  Wave-uniform control flow.
+template <bool Live>
+__device__ __forceinline__ float recognize_frames(const float4* __restrict__ src, int T,
+                                                  const float* __restrict__ transitions,
+                                                  const float* __restrict__ initial, uint32_t* __restrict__ out,
+                                                  const Ring& live, float4 (&stage)[2][CHUNK_VEC], int lane)
+{
+    const bool state = lane < NP;
+    const int s[1] = {state ? lane : 0};                       // the identity; lanes 40 .. 63 run along on phoneme 0
+    float a[NP];                                               // column `lane` of the transitions
+#pragma unroll
+    for (int p = 0; p < NP; ++p) a[p] = state ? transitions[p * NP + lane] : -INFINITY;
+    const float stay = state ? transitions[lane * NP + lane] : -INFINITY;
+    const float first = !state ? -INFINITY : initial ? initial[lane] : 0.f;
+    const int base = Live ? live.base : 0;
+    const int words = Live ? live.window / BACK : 0;           // rows of the ring
+    int word = Live ? base % live.window / BACK : 0;           // the row of the frame in hand
+    float d = Live ? live.d[lane] : -INFINITY;
+    int anc = Live ? live.anc[lane] : 0;
+    // this lane's back-pointers of up to BACK frames.  (In a full ring the other bytes of a row that is taken up again
+    // or left partly filled are those of the frames W earlier, which are still in use: they are masked out here and
+    // left alone at the end.)
+    uint32_t packed = Live && base % BACK ? out[(size_t)word * 64 + lane] & ((1u << 8 * (base % BACK)) - 1u) : 0;
+    WALK_FRAMES(1, false, t, cur,
+        const int at = base + t;                               // the absolute frame
+        int from = lane;
+        if (at == 0) {                                         // (uniform)
+            d = cur[0] + first;
+        } else {
+            const float before = d;
+            float best = before + stay;                        // staying: what a switch has to beat
+            _Pragma("unroll") for (int p0 = 0; p0 < NP; p0 += 8) {
+                float c[8];                                    // eight at a time: the moves stand ahead of their uses
+                _Pragma("unroll") for (int j = 0; j < 8; ++j) c[j] = from_lane(before, p0 + j);
+                _Pragma("unroll") for (int j = 0; j < 8; ++j) c[j] += a[p0 + j];
+                _Pragma("unroll") for (int j = 0; j < 8; ++j) {    // ascending: the lowest of equal predecessors stays
+                    const bool better = c[j] > best;           // (p = lane repeats `best` or less: never taken)
+                    best = better ? c[j] : best;
+                    from = better ? p0 + j : from;
+                }
+            }
+            d = cur[0] + best;                                 // -inf + finite = -inf: never NaN
+        }
+        if (Live) anc = at == live.commit ? lane : __builtin_amdgcn_ds_bpermute(from << 2, anc);
+        packed |= (uint32_t)from << (8 * (at % BACK));
+        if (at % BACK == BACK - 1) {                           // (uniform)
+            out[(size_t)(Live ? word : t / BACK) * 64 + lane] = packed;
+            packed = 0;
+            if (Live) word = word + 1 == words ? 0 : word + 1;
+        })
+    if (Live) {                                                // the partial dword, its own bytes only
+        uint8_t* bytes = reinterpret_cast<uint8_t*>(out + (size_t)word * 64 + lane);
+        for (int b = 0; b < (base + T) % BACK; ++b) bytes[b] = (uint8_t)(packed >> 8 * b);
+    } else if (T % BACK) {
+        out[(size_t)(T / BACK) * 64 + lane] = packed;          // (uniform) the last, partial dword
+    }
+    if (Live) { live.d[lane] = d; live.anc[lane] = anc; }
+    return d;
+}
+
+// the first of the largest of the 40 states' `value` (strict >, ascending), wave-uniform: its state; *most is its value
+__device__ __forceinline__ int first_largest(float value, float* most) {
+    float sum = from_lane(value, 0);
+    int end = 0;
+#pragma unroll
+    for (int q = 1; q < NP; ++q) {
+        const float f = from_lane(value, q);
+        const bool better = f > sum;
+        sum = better ? f : sum;
+        end = better ? q : end;
+    }
+    *most = sum;
+    return end;
+}
+
 // grid (items), 64 threads.  initial and final_ may be null: all zeros.  An utterance whose length is impossible gets
 // total = NaN and runs = 0, one without a path total = -inf and runs = 0; every other its total, its end state in
 // `ends` and its back-pointers.
@@ -1009,52 +1101,12 @@ __global__ __launch_bounds__(64) void recognize_programme(const float* __restric
         if (lane == 0) { total[item] = NAN; runs[item] = 0; }
         return;
     }
-    const bool state = lane < NP;
-    const int s[1] = {state ? lane : 0};                       // the identity; lanes 40 .. 63 run along on phoneme 0
-    float a[NP];                                               // column `lane` of the transitions
-#pragma unroll
-    for (int p = 0; p < NP; ++p) a[p] = state ? transitions[p * NP + lane] : -INFINITY;
-    const float stay = state ? transitions[lane * NP + lane] : -INFINITY;
-    const float first = !state ? -INFINITY : initial ? initial[lane] : 0.f;
     const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
-    uint32_t* out = back + (size_t)item * (back_bytes(frames) / 4);
-    float d = -INFINITY;
-    uint32_t packed = 0;                                       // this lane's back-pointers of up to BACK frames
-    WALK_FRAMES(1, false, t, cur,
-        int from = lane;
-        if (t == 0) {                                          // (uniform)
-            d = cur[0] + first;
-        } else {
-            const float before = d;
-            float best = before + stay;                        // staying: what a switch has to beat
-            _Pragma("unroll") for (int p0 = 0; p0 < NP; p0 += 8) {
-                float c[8];                                    // eight at a time: the moves stand ahead of their uses
-                _Pragma("unroll") for (int j = 0; j < 8; ++j) c[j] = from_lane(before, p0 + j);
-                _Pragma("unroll") for (int j = 0; j < 8; ++j) c[j] += a[p0 + j];
-                _Pragma("unroll") for (int j = 0; j < 8; ++j) {    // ascending: the lowest of equal predecessors stays
-                    const bool better = c[j] > best;           // (p = lane repeats `best` or less: never taken)
-                    best = better ? c[j] : best;
-                    from = better ? p0 + j : from;
-                }
-            }
-            d = cur[0] + best;                                 // -inf + finite = -inf: never NaN
-        }
-        packed |= (uint32_t)from << (8 * (t % BACK));
-        if (t % BACK == BACK - 1) {                            // (uniform)
-            out[(size_t)(t / BACK) * 64 + lane] = packed;
-            packed = 0;
-        })
-    if (T % BACK) out[(size_t)(T / BACK) * 64 + lane] = packed;            // (uniform) the last, partial dword
-    const float last = d + (!state ? -INFINITY : final_ ? final_[lane] : 0.f);
-    float sum = from_lane(last, 0);
-    int end = 0;
-#pragma unroll
-    for (int q = 1; q < NP; ++q) {                             // wave-uniform: the first of the largest
-        const float f = from_lane(last, q);
-        const bool better = f > sum;
-        sum = better ? f : sum;
-        end = better ? q : end;
-    }
+    const float d = recognize_frames<false>(src, T, transitions, initial,
+                                            back + (size_t)item * (back_bytes(frames) / 4), Ring{}, stage, lane);
+    const float last = d + (lane >= NP ? -INFINITY : final_ ? final_[lane] : 0.f);
+    float sum;
+    const int end = first_largest(last, &sum);
     if (lane == 0) {
         total[item] = sum;
         if (sum > -INFINITY) ends[item] = end;
@@ -1130,6 +1182,350 @@ __global__ __launch_bounds__(64) void recognize_runs(const int* __restrict__ lab
     if (lane == 0) { runs[item] = base; out_starts[base] = T; }
 }
 
+// ---- live phoneme recognition (ppg_recognize_stream_*) ----
+//
+// The recogniser above carried across the pushes of a stream.  A stream has a position p (frames since its reset, frame
+// indices are absolute), a commit point c <= p (frames below c have had their label given out for good), D of frame
+// p-1, a ring of W frames (slot t % W) with the back-pointers, the prepared frames and the labels of the frames in
+// [c, p), one open run (label, start, fp32 sum and below) and the counter `forced`.
+//   Forward: recognize_frames<Live = true>, the body of recognize_programme: D and the back-pointers of every frame are
+//   the bits recognize_programme computes for the whole recording, whatever the pushes.
+//   Commit, once per stream and push, t = p-1, alive(q) = D[q] > -inf, path(q, u) = the state at frame u of the
+//   trace-back from q at t:
+//     natural  v = the largest u in [c, t] at which path(q, u) is the same for every alive q (none: v = c-1); frames
+//              c .. v get that label, c = v+1.  No state alive: nothing is committed.
+//     forced   only if p - c > max_lag = L after that: best = the first alive q with the largest D; frames c .. p-L-1
+//              get path(best, .); every q with path(q, p-L-1) != path(best, p-L-1) gets D[q] = -inf; forced grows by
+//              the frames committed this way; c = p-L.
+//     runs     every newly committed frame, in order, extends the open run (sum += e[t, label], below += e[t, label] -
+//              max[t], fp32 from 0.f: the order of align_score) or closes it and opens the next; a closed run is emitted
+//              as (phoneme, begin, end, sum / float(end - begin), below / float(end - begin)).
+//   A stream with (p - c) + length > W, a length outside [0, frames] or a position that would pass INT32_MAX is
+//   impossible: count = -1 and nothing else changes.  flush: F = D + final, last = the first of the largest, total =
+//   F[last]; if total > -inf everything up to p is committed along path(last, .); the open run is closed and emitted,
+//   total and forced are reported and the stream is reset.  reset: p = c = 0, D = -inf, no open run, forced = 0.
+// The caller owns the state: six blocks, each 256-byte aligned: the head of every stream (8 words), D (64 words), the
+// ancestors (64 words: anc[q] = path(q, c), see below), the back-pointer ring (64 B per frame, in rows of BACK frames),
+// the ring of prepared frames (176 B per frame) and the ring of labels (int32).  Five kernels beside align_prepare, one
+// wave per stream:
+//   recognize_stream_programme  copies the push's prepared frames into the ring and runs recognize_frames<true>, which
+//                               also carries the ancestors forward: anc[q] = q at frame c, else anc[from[q]], one
+//                               cross-lane move per frame.  If the alive states' ancestors differ, no u in [c, t] has
+//                               all alive paths in one state (paths that meet stay together), so unless a commit has
+//                               to be forced the commit kernel has nothing to give out and skips its walk.
+//   recognize_stream_commit     lane q walks its own path back from t, the rows through LDS 64 frames at a time as in
+//                               recognize_traceback; a ballot per frame finds v, frame p-L-1 forces; lane u % 64 keeps
+//                               frame u's label and the wave stores 64 at once; then the new labels 64 at a time, lane =
+//                               frame: a ballot finds where runs open, and the sums go in frame order over the lanes.
+//   recognize_stream_advance    one thread per stream, after the commit: p += length unless the stream was refused.
+//   recognize_stream_flush, recognize_stream_reset
+
+constexpr int HEAD = 8;                       // words of a stream's head
+struct RecognizeHead {
+    int position, commit, forced;
+    int label, start;                         // the open run: label = -1: none
+    float sum, below;
+    int reserved;
+};
+static_assert(sizeof(RecognizeHead) == HEAD * 4, "the head is 8 words");
+
+struct RecognizeStreamLayout {
+    size_t heads, d, anc, back, kept, labels, bytes;                // byte offsets into the state
+};
+
+// (65535 streams of 65536 frames are 1.0e12 bytes: inside a size_t)
+inline RecognizeStreamLayout recognize_stream_layout(int streams, int window) {
+    RecognizeStreamLayout w{};
+    const size_t slots = (size_t)streams * window;
+    size_t at = 0;
+    w.heads = at; at = align256(at + (size_t)streams * sizeof(RecognizeHead));
+    w.d = at; at = align256(at + (size_t)streams * 64 * sizeof(float));
+    w.anc = at; at = align256(at + (size_t)streams * 64 * sizeof(int));
+    w.back = at; at = align256(at + slots * 64);
+    w.kept = at; at = align256(at + slots * PREP * sizeof(float));
+    w.labels = at; at = align256(at + slots * sizeof(int));
+    w.bytes = at;
+    return w;
+}
+
+// what a stream may be asked to take; everything else gets count = -1 and touches nothing
+__device__ __forceinline__ bool pushable(int T, int frames, int p, int c, int window) {
+    return T >= 0 && T <= frames && c >= 0 && c <= p && T <= INT32_MAX - p && p - c <= window &&
+           T <= window - (p - c);
+}
+
+// grid (streams), 64 threads
+__global__ __launch_bounds__(64) void recognize_stream_programme(const float* __restrict__ logp, int frames,
+                                                                  const int* __restrict__ lengths,
+                                                                  const float* __restrict__ transitions,
+                                                                  const float* __restrict__ initial, int window,
+                                                                  const RecognizeHead* __restrict__ heads,
+                                                                  float* __restrict__ state_d,
+                                                                  int* __restrict__ state_anc,
+                                                                  uint32_t* __restrict__ back,
+                                                                  float4* __restrict__ kept)
+{
+    __shared__ float4 stage[2][CHUNK_VEC];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item], p = heads[item].position, c = heads[item].commit;
+    if (!pushable(T, frames, p, c, window) || T == 0) return;  // (uniform) refused, or the stream sits out the step
+    const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
+    float4* ring = kept + (size_t)item * window * PREP_VEC;
+    const int slot0 = p % window;
+    for (int idx = lane; idx < T * PREP_VEC; idx += 64) {      // T <= window: a slot wraps once at most
+        int slot = slot0 + idx / PREP_VEC;
+        slot = slot >= window ? slot - window : slot;
+        ring[(size_t)slot * PREP_VEC + idx % PREP_VEC] = src[idx];
+    }
+    recognize_frames<true>(src, T, transitions, initial, back + (size_t)item * window * (64 / 4),
+                           Ring{state_d + (size_t)item * 64, p, window, state_anc + (size_t)item * 64, c}, stage, lane);
+}
+
+// What a stream hands to its commit and gets back: the run outputs of one push or flush.
+struct Runs {
+    int* phonemes; int* begin; int* end; float* score; float* gop;         // this stream's `cap` slots; gop may be null
+    int cap, count;                                                        // count: closed here, written or not
+};
+
+// the open run ends in front of frame `end`.  Wave-uniform; lane 0 writes.
+__device__ __forceinline__ void close_run(const RecognizeHead& run, int end, Runs& out, int lane) {
+    if (lane == 0 && out.count < out.cap) {
+        const float count = (float)(end - run.start);
+        out.phonemes[out.count] = run.label;
+        out.begin[out.count] = run.start;
+        out.end[out.count] = end;
+        out.score[out.count] = run.sum / count;
+        if (out.gop) out.gop[out.count] = run.below / count;
+    }
+    ++out.count;
+}
+
+// The commit of one stream whose position is p (after the push): `head` holds its commit point, open run and counter
+// and gets the new ones.  `lead` is the state whose path gives the labels: the best alive state of a push, the end state
+// of a flush, or -1 if there is none (nothing is committed then).  Flush: everything up to p goes along that path and
+// nothing is forced.  Otherwise the natural and the forced commit of the text above, and the ancestors at the new commit
+// point are left for the next push.  Wave-uniform control flow.
+template <bool Flush>
+__device__ __forceinline__ void commit(RecognizeHead& head, int p, int lead, bool alive, int max_lag, int window,
+                                       float* __restrict__ state_d, int* __restrict__ state_anc,
+                                       const uint32_t* __restrict__ back,
+                                       const float* __restrict__ kept, int* __restrict__ labels, Runs& out,
+                                       uint4 (&rows)[BACK_VEC], int lane)
+{
+    const int c = head.commit, t = p - 1;
+    const int force = Flush ? -1 : p - max_lag - 1;            // the frame a forced commit reaches up to
+    int fresh = c, natural = c;                                // the new commit point; what the natural commit gives
+    // the alive states' ancestors at c differ, so their paths meet nowhere in [c, t]: nothing to commit unless by force
+    bool apart = false;
+    if (!Flush && lead >= 0) {
+        const int anc = state_anc[lane];
+        apart = __ballot(alive && anc != __builtin_amdgcn_readlane(anc, lead)) != 0 && p - c <= max_lag;
+    }
+    if (lead >= 0 && t >= c && !apart) {                       // (uniform)
+        constexpr int PER = BACK_VEC / 64;
+        const uint4* src = reinterpret_cast<const uint4*>(back);
+        uint4 next[PER];
+        auto load = [&](int chunk) {                           // rows of frames chunk * WALK ..., those of [c, t] only
+            const int first = chunk * WALK;
+            const int low = (max(c, first) - first) / BACK, high = (min(t, first | (WALK - 1)) - first) / BACK;
+            const size_t at = (size_t)(first % window / BACK) * (BACK_ROW / 16);
+#pragma unroll
+            for (int u = 0; u < PER; ++u) {
+                const int idx = u * 64 + lane, row = idx / (BACK_ROW / 16);
+                next[u] = row >= low && row <= high ? src[at + idx] : make_uint4(0, 0, 0, 0);
+            }
+        };
+        bool agreed = Flush, committing = Flush;
+        if (Flush) fresh = natural = p;
+        int n = lane;                                          // lane q's state at frame u of its own path
+        int above = lane, fresh_anc = lane;                    // ... at frame u + 1; ... at the new commit point
+        int chunk = t / WALK;
+        const int last = c / WALK;
+        load(chunk);
+        for (; chunk >= last; --chunk) {
+            __syncthreads();                                   // the walk over the previous refill is over
+#pragma unroll
+            for (int u = 0; u < PER; ++u) rows[u * 64 + lane] = next[u];
+            __syncthreads();
+            if (chunk > last) load(chunk - 1);
+            const uint8_t* row = reinterpret_cast<const uint8_t*>(rows);
+            const int high = min(t, chunk * WALK | (WALK - 1)), low = max(c, chunk * WALK);
+            int mine = -1;
+            for (int u = high; u >= low; --u) {
+                const int here = __builtin_amdgcn_readlane(n, lead);       // the label of frame u, if it is given out
+                if (!agreed && __ballot(alive && n != here) == 0) {        // every alive path is in one state
+                    agreed = true;
+                    natural = u + 1;
+                }
+                if (!committing && (agreed || u == force)) {
+                    committing = true;
+                    fresh = u + 1;
+                    fresh_anc = above;
+                    if (!agreed && alive && n != here) state_d[lane] = -INFINITY;  // forced: the other paths end
+                }
+                if (committing && lane == (u & (WALK - 1))) mine = here;
+                above = n;
+                // frame u's predecessor on this lane's path (frame c's is not needed)
+                if (u > c) n = row[((u & (WALK - 1)) / BACK * 64 + n) * BACK + u % BACK] & 63;
+            }
+            if (mine >= 0) labels[(chunk * WALK + lane) % window] = mine;
+        }
+        if (!Flush) head.forced += fresh - natural;
+        if (!Flush && committing) state_anc[lane] = fresh_anc;
+    }
+    __threadfence_block();
+    __syncthreads();                                           // the labels are there for every lane
+    // the newly committed frames c .. fresh-1, 64 at a time: lane = frame
+    const int count = fresh - c, slot0 = c % window;
+    int carry = head.label;
+    for (int k0 = 0; k0 < count; k0 += 64) {                   // (uniform)
+        const int k = k0 + lane;
+        int slot = slot0 + k;
+        slot = slot >= window ? slot - window : slot;
+        int label = -2;
+        float e = 0.f, top = 0.f;
+        if (k < count) {
+            label = min(max(labels[slot], 0), NP - 1);
+            e = kept[(size_t)slot * PREP + label];
+            top = kept[(size_t)slot * PREP + NP];
+        }
+        const float under = e - top;                           // exactly 0 where the label is the frame's maximum
+        const unsigned long long opens = __ballot(k < count && label != lane_up(label, carry));
+        const int here = min(64, count - k0);
+        for (int j = 0; j < here; ++j) {                       // in frame order: every lane keeps the same sums
+            if ((opens >> j) & 1) {
+                if (head.label >= 0) close_run(head, c + k0 + j, out, lane);
+                head.label = __builtin_amdgcn_readlane(label, j);
+                head.start = c + k0 + j;
+                head.sum = head.below = 0.f;
+            }
+            head.sum += from_lane(e, j);
+            head.below += from_lane(under, j);
+        }
+        carry = __builtin_amdgcn_readlane(label, 63);
+    }
+    head.commit = fresh;
+}
+
+// slots at or past the runs written: -1 / NaN
+__device__ __forceinline__ void fill_runs(const Runs& out, int lane) {
+    for (int h = min(out.count, out.cap) + lane; h < out.cap; h += 64) {
+        out.phonemes[h] = out.begin[h] = out.end[h] = -1;
+        out.score[h] = NAN;
+        if (out.gop) out.gop[h] = NAN;
+    }
+}
+
+__device__ __forceinline__ Runs runs_of(int item, int cap, int* phonemes, int* begin, int* end, float* score,
+                                        float* gop) {
+    const size_t at = (size_t)item * cap;
+    return Runs{phonemes + at, begin + at, end + at, score + at, gop ? gop + at : nullptr, cap, 0};
+}
+
+// grid (streams), 64 threads, after the programme and before the advance: the head still holds the old position.
+__global__ __launch_bounds__(64) void recognize_stream_commit(int frames, const int* __restrict__ lengths, int window,
+                                                               int max_lag, RecognizeHead* __restrict__ heads,
+                                                               float* __restrict__ state_d,
+                                                               int* __restrict__ state_anc,
+                                                               const uint32_t* __restrict__ back,
+                                                               const float* __restrict__ kept,
+                                                               int* __restrict__ labels, int cap,
+                                                               int* __restrict__ phonemes, int* __restrict__ begin,
+                                                               int* __restrict__ end, float* __restrict__ score,
+                                                               float* __restrict__ gop, int* __restrict__ count)
+{
+    __shared__ uint4 rows[BACK_VEC];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item];
+    RecognizeHead head = heads[item];
+    if (!pushable(T, frames, head.position, head.commit, window)) {        // (uniform)
+        if (lane == 0) count[item] = -1;
+        return;
+    }
+    float* d = state_d + (size_t)item * 64;
+    const float mine = d[lane];
+    float most;
+    const int best = first_largest(mine, &most);
+    Runs out = runs_of(item, cap, phonemes, begin, end, score, gop);
+    commit<false>(head, head.position + T, most > -INFINITY ? best : -1, mine > -INFINITY, max_lag, window, d,
+                  state_anc + (size_t)item * 64,
+                  back + (size_t)item * window * (64 / 4), kept + (size_t)item * window * PREP,
+                  labels + (size_t)item * window, out, rows, lane);
+    if (lane == 0) {
+        heads[item] = head;                                    // (the position is the advance's to move)
+        count[item] = out.count;
+    }
+    fill_runs(out, lane);
+}
+
+// grid (ceil(streams / 64)), 64 threads: thread = stream.  The commit has said whether the stream took its frames.
+__global__ __launch_bounds__(64) void recognize_stream_advance(int streams, const int* __restrict__ lengths,
+                                                                const int* __restrict__ count,
+                                                                RecognizeHead* __restrict__ heads)
+{
+    const int item = blockIdx.x * 64 + threadIdx.x;
+    if (item >= streams) return;
+    if (count[item] >= 0) heads[item].position += lengths[item];
+}
+
+// a stream at frame 0.  Wave-uniform; every lane writes its D and its ancestor.
+__device__ __forceinline__ void restart(RecognizeHead* head, float* d, int* anc, int lane) {
+    d[lane] = -INFINITY;
+    anc[lane] = lane;
+    if (lane == 0) *head = RecognizeHead{0, 0, 0, -1, 0, 0.f, 0.f, 0};
+}
+
+// grid (streams), 64 threads.  A stream `which` leaves out gets count = 0, total = NaN, forced = -1 and keeps its state.
+__global__ __launch_bounds__(64) void recognize_stream_flush(int window, const float* __restrict__ final_,
+                                                              const int* __restrict__ which,
+                                                              RecognizeHead* __restrict__ heads,
+                                                              float* __restrict__ state_d,
+                                                              int* __restrict__ state_anc,
+                                                              const uint32_t* __restrict__ back,
+                                                              const float* __restrict__ kept,
+                                                              int* __restrict__ labels, int cap,
+                                                              int* __restrict__ phonemes, int* __restrict__ begin,
+                                                              int* __restrict__ end, float* __restrict__ score,
+                                                              float* __restrict__ gop, int* __restrict__ count,
+                                                              float* __restrict__ total, int* __restrict__ forced)
+{
+    __shared__ uint4 rows[BACK_VEC];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    Runs out = runs_of(item, cap, phonemes, begin, end, score, gop);
+    RecognizeHead head = heads[item];
+    const bool meant = !which || which[item] != 0;
+    // (a head that no reset or push of this library left gives nothing out and is reset)
+    const bool sound = head.commit >= 0 && head.commit <= head.position && head.position - head.commit <= window;
+    float sum = NAN;
+    if (meant && sound) {                                      // (uniform)
+        float* d = state_d + (size_t)item * 64;
+        const float last = d[lane] + (lane >= NP ? -INFINITY : final_ ? final_[lane] : 0.f);
+        const int state = first_largest(last, &sum);
+        commit<true>(head, head.position, sum > -INFINITY ? state : -1, false, 0, window, d, nullptr,
+                     back + (size_t)item * window * (64 / 4), kept + (size_t)item * window * PREP,
+                     labels + (size_t)item * window, out, rows, lane);
+        if (head.label >= 0) close_run(head, head.commit, out, lane);
+    }
+    if (lane == 0) {
+        count[item] = out.count;
+        total[item] = meant && sound ? sum : NAN;
+        forced[item] = meant && sound ? head.forced : -1;
+    }
+    fill_runs(out, lane);
+    if (meant) restart(heads + item, state_d + (size_t)item * 64, state_anc + (size_t)item * 64, lane);
+}
+
+// grid (streams), 64 threads
+__global__ __launch_bounds__(64) void recognize_stream_reset(const int* __restrict__ which,
+                                                              RecognizeHead* __restrict__ heads,
+                                                              float* __restrict__ state_d,
+                                                              int* __restrict__ state_anc)
+{
+    const int item = blockIdx.x;
+    if (which && which[item] == 0) return;                     // (uniform)
+    restart(heads + item, state_d + (size_t)item * 64, state_anc + (size_t)item * 64, threadIdx.x);
+}
+
 // ---- the rungs the host entries share, in the order every entry takes them.  Each returns PPG_OK or has left its
 // message; nothing is launched before the last of an entry's checks has passed. ----
 
@@ -1153,6 +1549,36 @@ int check_stream_state(const char* what, const void* state, int streams, int que
     if (const int rc = check_queries(what, queries, max_phonemes)) return rc;
     if (reinterpret_cast<uintptr_t>(state) % 16)
         return ppg::fail_message(PPG_EINVAL, "%s: the state must be 16-byte aligned", what);
+    return PPG_OK;
+}
+
+bool recognize_stream_sizes_fine(int streams, int window) {
+    return streams > 0 && streams <= PPG_RECOGNIZE_STREAM_MAX_STREAMS && window >= PPG_RECOGNIZE_STREAM_MIN_WINDOW &&
+           window <= PPG_RECOGNIZE_STREAM_MAX_WINDOW && window % 64 == 0;
+}
+
+// the checks the three entries of the live recogniser share: the state and its geometry
+int check_recognize_stream_state(const char* what, const void* state, int streams, int window) {
+    if (!state) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (!recognize_stream_sizes_fine(streams, window))
+        return ppg::fail_message(PPG_EINVAL, "%s: %d streams of a window of %d frames: 1 to %d streams, a window that "
+                                 "is a multiple of 64 from %d to %d", what, streams, window,
+                                 PPG_RECOGNIZE_STREAM_MAX_STREAMS, PPG_RECOGNIZE_STREAM_MIN_WINDOW,
+                                 PPG_RECOGNIZE_STREAM_MAX_WINDOW);
+    if (reinterpret_cast<uintptr_t>(state) % 16)
+        return ppg::fail_message(PPG_EINVAL, "%s: the state must be 16-byte aligned", what);
+    return PPG_OK;
+}
+
+// the words a kernel reads and writes: none NULL but those that may be, every one on a 4-byte boundary
+int check_words(const char* what, std::initializer_list<const void*> required,
+                std::initializer_list<const void*> may_be_null) {
+    for (const void* pointer : required)
+        if (!pointer) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    for (const auto& list : {required, may_be_null})
+        for (const void* pointer : list)
+            if (reinterpret_cast<uintptr_t>(pointer) % 4)
+                return ppg::fail_message(PPG_EINVAL, "%s: inputs and outputs must be 4-byte aligned", what);
     return PPG_OK;
 }
 
@@ -1418,6 +1844,85 @@ int ppg_search_stream_flush(int device, void* state, int streams, int queries, i
                        reinterpret_cast<Detector*>(static_cast<char*>(state) + w.detectors), begin, end, total, mean,
                        count);
     return launched("search_stream_flush");
+}
+
+size_t ppg_recognize_stream_state_bytes(int streams, int window) {
+    return recognize_stream_sizes_fine(streams, window) ? recognize_stream_layout(streams, window).bytes : 0;
+}
+
+size_t ppg_recognize_stream_workspace_bytes(int streams, int frames) {
+    if (streams <= 0 || streams > PPG_RECOGNIZE_STREAM_MAX_STREAMS || frames <= 0 || frames > PPG_RECOGNIZE_MAX_FRAMES)
+        return 0;
+    return prepared_bytes(streams, frames);
+}
+
+int ppg_recognize_stream_reset(int device, void* state, int streams, int window, const int32_t* which, void* stream) {
+    if (const int rc = check_recognize_stream_state("recognize_stream_reset", state, streams, window)) return rc;
+    if (const int rc = check_words("recognize_stream_reset", {}, {which})) return rc;
+    if (const int rc = select_device(device)) return rc;
+    const RecognizeStreamLayout w = recognize_stream_layout(streams, window);
+    char* st = static_cast<char*>(state);
+    hipLaunchKernelGGL(recognize_stream_reset, dim3(streams), dim3(64), 0, static_cast<hipStream_t>(stream), which,
+                       reinterpret_cast<RecognizeHead*>(st + w.heads), reinterpret_cast<float*>(st + w.d),
+                       reinterpret_cast<int*>(st + w.anc));
+    return launched("recognize_stream_reset");
+}
+
+int ppg_recognize_stream_push(int device, void* state, int streams, int window, const float* ppg, int frames,
+                              const int32_t* lengths, const float* transitions, const float* initial, int max_lag,
+                              int cap, int32_t* phonemes, int32_t* begin, int32_t* end, float* score, float* gop,
+                              int32_t* count, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "recognize_stream_push";
+    if (const int rc = check_recognize_stream_state(what, state, streams, window)) return rc;
+    if (const int rc = check_words(what, {ppg, lengths, transitions, phonemes, begin, end, score, count, workspace},
+                                   {initial, gop}))
+        return rc;
+    if (frames < 1 || frames > PPG_RECOGNIZE_MAX_FRAMES)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d frames, must be 1 .. %d", what, frames, PPG_RECOGNIZE_MAX_FRAMES);
+    if (max_lag < 0 || max_lag >= window)
+        return ppg::fail_message(PPG_EINVAL, "%s: max_lag = %d, must be 0 .. window - 1 = %d", what, max_lag,
+                                 window - 1);
+    if (cap < 1) return ppg::fail_message(PPG_EINVAL, "%s: cap = %d, must be at least 1", what, cap);
+    if (const int rc = check_workspace(what, workspace, workspace_bytes, prepared_bytes(streams, frames))) return rc;
+    if (const int rc = select_device(device)) return rc;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const RecognizeStreamLayout w = recognize_stream_layout(streams, window);
+    char* st = static_cast<char*>(state);
+    RecognizeHead* heads = reinterpret_cast<RecognizeHead*>(st + w.heads);
+    float* d = reinterpret_cast<float*>(st + w.d);
+    uint32_t* back = reinterpret_cast<uint32_t*>(st + w.back);
+    float* kept = reinterpret_cast<float*>(st + w.kept);
+    float* logp = static_cast<float*>(workspace);
+    hipLaunchKernelGGL(align_prepare, dim3((frames + 63) / 64, streams), dim3(64), 0, s, ppg, frames, lengths, logp);
+    hipLaunchKernelGGL(recognize_stream_programme, dim3(streams), dim3(64), 0, s, logp, frames, lengths, transitions,
+                       initial, window, heads, d, reinterpret_cast<int*>(st + w.anc), back,
+                       reinterpret_cast<float4*>(kept));
+    hipLaunchKernelGGL(recognize_stream_commit, dim3(streams), dim3(64), 0, s, frames, lengths, window, max_lag, heads,
+                       d, reinterpret_cast<int*>(st + w.anc), back, kept, reinterpret_cast<int*>(st + w.labels), cap,
+                       phonemes, begin, end, score, gop, count);
+    hipLaunchKernelGGL(recognize_stream_advance, dim3((streams + 63) / 64), dim3(64), 0, s, streams, lengths, count,
+                       heads);
+    return launched(what);
+}
+
+int ppg_recognize_stream_flush(int device, void* state, int streams, int window, const float* final_,
+                               const int32_t* which, int cap, int32_t* phonemes, int32_t* begin, int32_t* end,
+                               float* score, float* gop, int32_t* count, float* total, int32_t* forced, void* stream) {
+    const char* what = "recognize_stream_flush";
+    if (const int rc = check_recognize_stream_state(what, state, streams, window)) return rc;
+    if (const int rc = check_words(what, {phonemes, begin, end, score, count, total, forced}, {final_, which, gop}))
+        return rc;
+    if (cap < 1) return ppg::fail_message(PPG_EINVAL, "%s: cap = %d, must be at least 1", what, cap);
+    if (const int rc = select_device(device)) return rc;
+    const RecognizeStreamLayout w = recognize_stream_layout(streams, window);
+    char* st = static_cast<char*>(state);
+    hipLaunchKernelGGL(recognize_stream_flush, dim3(streams), dim3(64), 0, static_cast<hipStream_t>(stream), window,
+                       final_, which, reinterpret_cast<RecognizeHead*>(st + w.heads),
+                       reinterpret_cast<float*>(st + w.d), reinterpret_cast<int*>(st + w.anc),
+                       reinterpret_cast<const uint32_t*>(st + w.back), reinterpret_cast<const float*>(st + w.kept),
+                       reinterpret_cast<int*>(st + w.labels), cap, phonemes, begin, end, score, gop, count, total,
+                       forced);
+    return launched(what);
 }
 
 }  // extern "C"

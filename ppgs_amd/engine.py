@@ -185,6 +185,19 @@ SYMBOLS = {
     'ppg_search_stream_flush': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_recognize_stream_state_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    'ppg_recognize_stream_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    'ppg_recognize_stream_reset': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_recognize_stream_push': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+        ctypes.c_void_p]),
+    'ppg_recognize_stream_flush': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_metrics_state_bytes': (ctypes.c_size_t, []),
     'ppg_metrics_reset': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_metrics_update': (ctypes.c_int, [
@@ -1018,6 +1031,75 @@ def search_stream_flush(state, streams, queries, most, which=None):
             begin.data_ptr(), end.data_ptr(), total.data_ptr(), mean.data_ptr(), count.data_ptr(),
             torch.cuda.current_stream().cuda_stream))
     return begin, end, total, mean, count
+
+
+RECOGNIZE_STREAM_MIN_WINDOW = 64     # PPG_RECOGNIZE_STREAM_MIN_WINDOW
+RECOGNIZE_STREAM_MAX_WINDOW = 65536  # PPG_RECOGNIZE_STREAM_MAX_WINDOW
+RECOGNIZE_STREAM_MAX_STREAMS = 65535  # PPG_RECOGNIZE_STREAM_MAX_STREAMS
+
+
+def recognize_stream_state(device, streams, window):
+    """The device block of a live recogniser (ppg_recognize_stream_*), reset: `streams` streams with a ring of `window`
+    frames each.  uint8; its owner passes it to the three calls below with the same two numbers."""
+    size = library().ppg_recognize_stream_state_bytes(streams, window)
+    if size == 0:
+        raise ValueError(f'a live recogniser takes 1 to {RECOGNIZE_STREAM_MAX_STREAMS} streams and a window that is a '
+                         f'multiple of 64 from {RECOGNIZE_STREAM_MIN_WINDOW} to {RECOGNIZE_STREAM_MAX_WINDOW}, got '
+                         f'{streams} and {window}')
+    state = torch.empty((size,), dtype=torch.uint8, device=device)
+    recognize_stream_reset(state, streams, window)
+    return state
+
+
+def recognize_stream_reset(state, streams, window, which=None):
+    """ppg_recognize_stream_reset on the current stream: `which` is None (all) or a device int32 (streams,) of flags."""
+    with torch.cuda.device(state.device):
+        _check(library().ppg_recognize_stream_reset(
+            state.device.index, state.data_ptr(), streams, window, which.data_ptr() if which is not None else None,
+            torch.cuda.current_stream().cuda_stream))
+
+
+def _run_outputs(device, streams, cap, want_gop):
+    return (torch.empty((streams, cap), dtype=torch.int32, device=device),
+            torch.empty((streams, cap), dtype=torch.int32, device=device),
+            torch.empty((streams, cap), dtype=torch.int32, device=device),
+            torch.empty((streams, cap), dtype=torch.float32, device=device),
+            torch.empty((streams, cap), dtype=torch.float32, device=device) if want_gop else None,
+            torch.empty((streams,), dtype=torch.int32, device=device))
+
+
+def recognize_stream_push(state, window, ppg, lengths, transitions, initial, max_lag, cap, workspace, want_gop=True):
+    """ppg_recognize_stream_push on the current stream: ppg (streams, 40, frames) fp32, lengths (streams,) int32,
+    transitions (40, 40) and initial (40,) or None fp32, all contiguous on the state's device; workspace a uint8 tensor
+    there -> phonemes, begin, end (streams, cap) int32, score, gop (streams, cap) fp32 (gop None without want_gop) and
+    count (streams,) int32: the runs closed in this push; slots at or past it are -1 / NaN."""
+    device = state.device
+    streams, frames = ppg.shape[0], ppg.shape[2]
+    phonemes, begin, end, score, gop, count = _run_outputs(device, streams, cap, want_gop)
+    with torch.cuda.device(device):
+        _check(library().ppg_recognize_stream_push(
+            device.index, state.data_ptr(), streams, window, ppg.data_ptr(), frames, lengths.data_ptr(),
+            transitions.data_ptr(), initial.data_ptr() if initial is not None else None, max_lag, cap,
+            phonemes.data_ptr(), begin.data_ptr(), end.data_ptr(), score.data_ptr(),
+            gop.data_ptr() if want_gop else None, count.data_ptr(), workspace.data_ptr(), workspace.numel(),
+            torch.cuda.current_stream().cuda_stream))
+    return phonemes, begin, end, score, gop, count
+
+
+def recognize_stream_flush(state, streams, window, final, cap, which=None, want_gop=True):
+    """ppg_recognize_stream_flush on the current stream -> the run outputs of recognize_stream_push, and total fp32 and
+    forced int32 (streams,)."""
+    device = state.device
+    phonemes, begin, end, score, gop, count = _run_outputs(device, streams, cap, want_gop)
+    total = torch.empty((streams,), dtype=torch.float32, device=device)
+    forced = torch.empty((streams,), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _check(library().ppg_recognize_stream_flush(
+            device.index, state.data_ptr(), streams, window, final.data_ptr() if final is not None else None,
+            which.data_ptr() if which is not None else None, cap, phonemes.data_ptr(), begin.data_ptr(),
+            end.data_ptr(), score.data_ptr(), gop.data_ptr() if want_gop else None, count.data_ptr(),
+            total.data_ptr(), forced.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return phonemes, begin, end, score, gop, count, total, forced
 
 
 METRICS_FIXED_POINT = 2.0 ** 32        # the real-valued accumulators of PpgMetricsState count units of 2^-32
