@@ -184,11 +184,16 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, const AttnItem& ite
             exp_block(std::false_type{}, t, r - 1, 0.f, s, pf);
         }
     };
-    // some p of the tile is past the ceiling: move the shift to the tile's maximum
+    // some p of the tile is past the ceiling: move the shift to the tile's maximum -- of the QUERIES that are past it (one of
+    // a query's four lanes is).  The wave's other queries keep their shift, their p and their sums untouched: what a query's
+    // row comes to must not depend on the rows beside it (a stream recomputes the final rows of its frontier block beside
+    // other neighbours every step, and "a recomputed row gives the same bits").
     auto rebase = [&](f32x4 (&s)[KB][NTQ], f32x4 (&nxt)[KB][NTQ], u32x4 (&pf)[PG][NTQ]) {
 #pragma unroll
         for (int t = 0; t < NTQ; ++t) {
             const float d = fmaxf(tile_max(t, s), 0.f);       // (a fully masked tile: -inf -> 0)
+            // (both cross-lane reductions above the divergent branch)
+            if (!(wave_max_g(psum[t]) > (a.rebase_always ? 1.0f : P::kProbCeil))) continue;
             const float alpha = __builtin_amdgcn_exp2f(-d);
             lrun[t] *= alpha;
 #pragma unroll

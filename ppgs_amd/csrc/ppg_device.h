@@ -457,6 +457,10 @@ struct FfnArgs {
     int* tickets;             // split-hidden mode, 16 tokens per wave, hidden 256, <= 8 splits: one zeroed counter per token tile --
                               // the LAST of a tile's workgroups to arrive sums the partial rows and applies LayerNorm-2
                               // itself (no ffn_reduce_ln_kernel launch); null: the two-pass form
+    int groups;               // row-mapped launches (streams), splits == 1, no `partial`: the workgroup walks ALL hidden chunks but
+                              // closes its accumulator every chunks / groups of them, adds the closed sums in order, then bias +
+                              // residual, and applies LayerNorm-2 -- the arithmetic of `groups` hidden splits and the reduce
+                              // pass, bit for bit, in one launch (ffn_closed_kernel, hidden 256); 0 / 1: off
 };
 
 // Memory laid out for the feature-split layer kernel (160-token workgroup tiles):

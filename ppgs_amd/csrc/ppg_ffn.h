@@ -25,6 +25,19 @@ namespace {
 // Rows m0 .. m0 + R - 1 (dense partial rows slot0 ..) of the split-hidden FFN: b2 + residual + the partial sums in
 // split order, LayerNorm-2, X and its operand copy -- ffn_reduce_ln_kernel's arithmetic, R rows of one wave with all
 // their loads in flight together (hidden 256: a lane owns features 4 lane .. + 3 of every row).
+// LayerNorm-2 of the split-hidden FFN, per float4 of a row's features: written once, for the reduce pass and for the
+// closed-groups kernel's own epilogue (ffn_body), which must give a row the same bits.
+__device__ __forceinline__ float ln_quad_sum(const float4& v) { return (v.x + v.y) + (v.z + v.w); }
+__device__ __forceinline__ float ln_quad_sq(const float4& v, float mean) {
+    const float d0 = v.x - mean, d1 = v.y - mean, d2 = v.z - mean, d3 = v.w - mean;
+    return (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+}
+__device__ __forceinline__ float ln_rstd(float sq, int H) { return 1.0f / sqrtf(sq / (float)H + kLnEps); }
+__device__ __forceinline__ float4 ln_quad_out(const float4& v, float mean, float rstd, const float4& gv, const float4& ev) {
+    return make_float4((v.x - mean) * rstd * gv.x + ev.x, (v.y - mean) * rstd * gv.y + ev.y,
+                       (v.z - mean) * rstd * gv.z + ev.z, (v.w - mean) * rstd * gv.w + ev.w);
+}
+
 template <class P, int R>
 __device__ __forceinline__ void reduce_ln_rows(const FfnArgs& a, int splits, int slot0, int m0, int lane, size_t stride) {
     constexpr int H = 256;
@@ -43,31 +56,30 @@ __device__ __forceinline__ void reduce_ln_rows(const FfnArgs& a, int splits, int
     for (int j = 0; j < R; ++j) xv[j] = *reinterpret_cast<const float4*>(a.X + (size_t)min(m0 + j, a.M - 1) * H + n);
 #pragma unroll
     for (int j = 0; j < R; ++j) {
-        float4 acc = make_float4(bv.x + xv[j].x, bv.y + xv[j].y, bv.z + xv[j].z, bv.w + xv[j].w);
+        // (row map = streaming: the partial sums first, from zero, bias + residual last -- the order in which a workgroup
+        // that walks all hidden groups itself adds them (FfnArgs::groups), so that both forms give a row the same bits)
+        const float4 rx = make_float4(bv.x + xv[j].x, bv.y + xv[j].y, bv.z + xv[j].z, bv.w + xv[j].w);
+        float4 acc = a.rowmap ? make_float4(0.f, 0.f, 0.f, 0.f) : rx;
 #pragma unroll
         for (int k = 0; k < 8; ++k)
             if (k < splits) { acc.x += p[j][k].x; acc.y += p[j][k].y; acc.z += p[j][k].z; acc.w += p[j][k].w; }
-        float sum = (acc.x + acc.y) + (acc.z + acc.w);
+        if (a.rowmap) { acc.x += rx.x; acc.y += rx.y; acc.z += rx.z; acc.w += rx.w; }
+        float sum = ln_quad_sum(acc);
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
         const float mean = sum / (float)H;
-        const float d0 = acc.x - mean, d1 = acc.y - mean, d2 = acc.z - mean, d3 = acc.w - mean;
-        float sq = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        float sq = ln_quad_sq(acc, mean);
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off);
-        const float rstd = 1.0f / sqrtf(sq / (float)H + kLnEps);
-        const float y0 = (acc.x - mean) * rstd * gv.x + ev.x;
-        const float y1 = (acc.y - mean) * rstd * gv.y + ev.y;
-        const float y2 = (acc.z - mean) * rstd * gv.z + ev.z;
-        const float y3 = (acc.w - mean) * rstd * gv.w + ev.w;
+        const float4 y = ln_quad_out(acc, mean, ln_rstd(sq, H), gv, ev);
         const int m = m0 + j;
         if (m >= a.M) continue;
-        *reinterpret_cast<float4*>(a.X + (size_t)m * H + n) = make_float4(y0, y1, y2, y3);
-        if constexpr (P::kIsBF16 || P::kSplit) store4<P>(a.Xb + (size_t)m * H * P::kBytes + P::row_byte(n), y0, y1, y2, y3);
+        *reinterpret_cast<float4*>(a.X + (size_t)m * H + n) = y;
+        if constexpr (P::kIsBF16 || P::kSplit) store4<P>(a.Xb + (size_t)m * H * P::kBytes + P::row_byte(n), y.x, y.y, y.z, y.w);
     }
 }
 
-template <class P, int NTA, int NTB, int NBH, bool OP, bool QKV, int ROLE>
+template <class P, int NTA, int NTB, int NBH, bool OP, bool QKV, int ROLE, bool CLOSED = false>
 __device__ __forceinline__ void ffn_body(const FfnArgs& a, char* smem, const int tok0) {
     constexpr int NT = NTB;                         // token blocks of everything outside the chunk loop
     constexpr int NTX = NTA > NTB ? NTA : NTB;      // operand fragment sets held
@@ -361,6 +373,21 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, char* smem, const int
         stamp(c, 5);
     };
 
+    // Closed groups (FfnArgs::groups; row-mapped launches of 16 tokens per wave): the accumulator is closed every
+    // `group_len` chunks -- added to `ysum` and zeroed -- so that ysum is built exactly as ffn_reduce_ln_kernel builds it from
+    // the partial rows of `groups` hidden splits, each of which sums its chunks from zero in this order.
+    // It is an instantiation of its own (ffn_closed_kernel): compiled into the plain kernel, the second accumulator cost the
+    // small steps, which never use it, 3 .. 4 % of a step.
+    constexpr bool GROUPS = CLOSED;
+    static_assert(!CLOSED || (!OP && NT == 1 && NBH == 16 && ROLE == 0), "closed groups: the plain 16-token kernel at hidden 256");
+    f32x4 ysum[GROUPS ? NBH : 1];
+    const int group_len = GROUPS ? NC / max(a.groups, 1) : 0;
+    if constexpr (GROUPS) {
+#pragma unroll
+        for (int nb = 0; nb < NBH; ++nb) ysum[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    int group_left = group_len;
+
     f32x4 h0[HB][NTA], h1[HB][NTA];
     pstamp(13);
     dma_wait_barrier();
@@ -386,9 +413,62 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, char* smem, const int
         for (int hb = 0; hb < HB; ++hb)
 #pragma unroll
             for (int t = 0; t < NTA; ++t) h0[hb][t] = h1[hb][t];
+        if constexpr (GROUPS) {
+            if (group_len > 0 && --group_left == 0) {
+                group_left = group_len;
+#pragma unroll
+                for (int nb = 0; nb < NBH; ++nb) {
+                    ysum[nb] += yacc[nb][0];
+                    yacc[nb][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+            }
+        }
     }
 
     pstamp(9);
+    if constexpr (CLOSED) {
+        // The reduce pass's arithmetic on the closed sums, in this kernel's layout: bias + residual last, the row's 64
+        // float4 sums added in the reduce pass's butterfly order -- its lane q holds features 4 q .. 4 q + 3 and pairs q
+        // with q ^ 32, 16, .. 1; here float4 q = 8 (nb >> 1) + 2 g + (nb & 1), so that is nb ^ 8, 4, 2 inside the lane, the
+        // lane groups g ^ 2 and g ^ 1 (lanes ^ 32, ^ 16), and nb ^ 1 last.  No partial row, no reduce launch.
+        const int m = tok0 + idx;
+        const bool ok = m < a.M;
+        const float* xrow = a.X + (size_t)(ok ? m : 0) * H;
+        float4 v[NBH];
+#pragma unroll
+        for (int nb = 0; nb < NBH; ++nb) {
+            const int n = pair_feature(nb, g);
+            const float4 bv = *reinterpret_cast<const float4*>(lnp2 + n);
+            const float4 xv = *reinterpret_cast<const float4*>(xrow + n);
+            const float4 rx = make_float4(bv.x + xv.x, bv.y + xv.y, bv.z + xv.z, bv.w + xv.w);
+            v[nb] = make_float4(ysum[nb][0] + rx.x, ysum[nb][1] + rx.y, ysum[nb][2] + rx.z, ysum[nb][3] + rx.w);
+        }
+        auto row_sum = [&](auto quad) {
+            float half[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                float s = ((quad(0 + e) + quad(8 + e)) + (quad(4 + e) + quad(12 + e))) + ((quad(2 + e) + quad(10 + e)) + (quad(6 + e) + quad(14 + e)));
+                s += __shfl_xor(s, 32);
+                s += __shfl_xor(s, 16);
+                half[e] = s;
+            }
+            return half[0] + half[1];
+        };
+        static_assert(NBH == 16, "the butterfly order above is that of 64 float4 per row");
+        const float mean = row_sum([&](int nb) { return ln_quad_sum(v[nb]); }) / (float)H;
+        const float rstd = ln_rstd(row_sum([&](int nb) { return ln_quad_sq(v[nb], mean); }), H);
+        if (!ok) return;
+#pragma unroll
+        for (int nb = 0; nb < NBH; ++nb) {
+            const int n = pair_feature(nb, g);
+            const float4 gv = *reinterpret_cast<const float4*>(lnp2 + H + n);
+            const float4 ev = *reinterpret_cast<const float4*>(lnp2 + 2 * H + n);
+            const float4 y = ln_quad_out(v[nb], mean, rstd, gv, ev);
+            *reinterpret_cast<float4*>(a.X + (size_t)m * H + n) = y;
+            if constexpr (P::kIsBF16 || P::kSplit) store4<P>(a.Xb + (size_t)m * H * P::kBytes + P::row_byte(n), y.x, y.y, y.z, y.w);
+        }
+        return;
+    }
     if (a.partial != nullptr) {
         // split-hidden: raw partial sums, [split][token][feature] fp32.  Under a row map the rows are those of the
         // launch's slots, densely (the step's rows lie all over the token space: a split stride of the whole space put
@@ -401,9 +481,10 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& a, char* smem, const int
             if (m >= a.M) continue;
             const int pm = a.rowmap ? (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + idx : m;
 #pragma unroll
-            for (int nb = 0; nb < NBH; ++nb)
-                *reinterpret_cast<float4*>(part + (size_t)pm * H + pair_feature(nb, g)) =
-                    make_float4(yacc[nb][t][0], yacc[nb][t][1], yacc[nb][t][2], yacc[nb][t][3]);
+            for (int nb = 0; nb < NBH; ++nb) {
+                const f32x4 y = yacc[nb][t];
+                *reinterpret_cast<float4*>(part + (size_t)pm * H + pair_feature(nb, g)) = make_float4(y[0], y[1], y[2], y[3]);
+            }
         }
         if constexpr (NT == 1 && NBH == 16 && !OP) {
             if (a.tickets != nullptr) {
@@ -589,6 +670,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     ffn_body<P, NT, NT, NBH, OP, QKV, 0>(a, smem, tok0);
 }
 
+// The closed-groups form of the 16-token kernel at hidden 256 (FfnArgs::groups): row-mapped launches of big stream steps.
+template <class P>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void ffn_closed_kernel(FfnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tok0 = __builtin_amdgcn_readfirstlane(a.rowmap[blockIdx.x * 4 + wave]);
+    ffn_body<P, 1, 1, 16, false, false, 0, true>(a, smem, tok0);
+}
+
 // Mixed tiling: 160 tokens per workgroup = waves owning 3, 3, 2, 2 blocks of 16,
 // with the 2-block waves computing the phase A of their partner's third block
 // (ffn_body ROLE 1 / 2): every wave runs 5 block-phases per chunk instead of 6.
@@ -627,7 +717,8 @@ __global__ __launch_bounds__(256) void ffn_reduce_ln_kernel(FfnArgs a, int split
         const int n = h * 256 + lane * 4;
         const float4 bv = *reinterpret_cast<const float4*>(a.b2 + n);
         const float4 xv = *reinterpret_cast<const float4*>(a.X + (size_t)m * H + n);
-        float4 acc = make_float4(bv.x + xv.x, bv.y + xv.y, bv.z + xv.z, bv.w + xv.w);
+        const float4 rx = make_float4(bv.x + xv.x, bv.y + xv.y, bv.z + xv.z, bv.w + xv.w);
+        float4 acc = a.rowmap ? make_float4(0.f, 0.f, 0.f, 0.f) : rx;      // (row map: bias + residual last, see reduce_ln_rows)
         // the partial sums are added in split order, loaded 8 / 4 / 1 at a time:
         // one load latency per batch instead of one per split
         const float* part = a.partial + (size_t)(a.rowmap ? slot : m) * H + n;
@@ -646,41 +737,44 @@ __global__ __launch_bounds__(256) void ffn_reduce_ln_kernel(FfnArgs a, int split
         batch(std::integral_constant<int, 8>{});
         batch(std::integral_constant<int, 4>{});
         batch(std::integral_constant<int, 1>{});
+        if (a.rowmap) { acc.x += rx.x; acc.y += rx.y; acc.z += rx.z; acc.w += rx.w; }
         v[h] = acc;
-        sum += (acc.x + acc.y) + (acc.z + acc.w);
+        sum += ln_quad_sum(acc);
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
     const float mean = sum / (float)H;
     float sq = 0.f;
-    for (int h = 0; h < H / 256; ++h) {
-        const float d0 = v[h].x - mean, d1 = v[h].y - mean, d2 = v[h].z - mean, d3 = v[h].w - mean;
-        sq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-    }
+    for (int h = 0; h < H / 256; ++h) sq += ln_quad_sq(v[h], mean);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off);
-    const float rstd = 1.0f / sqrtf(sq / (float)H + kLnEps);
+    const float rstd = ln_rstd(sq, H);
     for (int h = 0; h < H / 256; ++h) {
         const int n = h * 256 + lane * 4;
         const float4 gv = *reinterpret_cast<const float4*>(a.gamma + n);
         const float4 ev = *reinterpret_cast<const float4*>(a.beta + n);
-        const float y0 = (v[h].x - mean) * rstd * gv.x + ev.x;
-        const float y1 = (v[h].y - mean) * rstd * gv.y + ev.y;
-        const float y2 = (v[h].z - mean) * rstd * gv.z + ev.z;
-        const float y3 = (v[h].w - mean) * rstd * gv.w + ev.w;
-        *reinterpret_cast<float4*>(a.X + (size_t)m * H + n) = make_float4(y0, y1, y2, y3);
-        if constexpr (P::kIsBF16 || P::kSplit) store4<P>(a.Xb + (size_t)m * H * P::kBytes + P::row_byte(n), y0, y1, y2, y3);
+        const float4 y = ln_quad_out(v[h], mean, rstd, gv, ev);
+        *reinterpret_cast<float4*>(a.X + (size_t)m * H + n) = y;
+        if constexpr (P::kIsBF16 || P::kSplit) store4<P>(a.Xb + (size_t)m * H * P::kBytes + P::row_byte(n), y.x, y.y, y.z, y.w);
     }
 }
 
 template <class P, int NT, int NBH, bool OP, bool QKV>
 hipError_t launch_ffn_t(const FfnArgs& a, hipStream_t s) {
     if (a.rowmap && NT != 1) return hipErrorInvalidValue;
+    // (closed groups: one workgroup per token tile walks all chunks; the plain 16-token kernel under a row map has the form)
+    if (a.groups > 1 && (NT != 1 || NBH != 16 || OP || !a.rowmap || a.partial || a.splits != 1 || a.tickets || (a.F / (32768 / (a.H * P::kBytes))) % a.groups))
+        return hipErrorInvalidValue;
     const dim3 blocks(a.rowmap ? (a.map_blocks + 3) / 4 : (a.M + 64 * NT - 1) / (64 * NT), a.partial ? a.splits : 1);
     auto kern = ffn_kernel<P, NT, NBH, OP, QKV>;
+    static ppg::LdsLimit closed_limit;
+    ppg::LdsLimit* which = nullptr;
+    if constexpr (NT == 1 && NBH == 16 && !OP && !QKV) {
+        if (a.groups > 1) { kern = ffn_closed_kernel<P>; which = &closed_limit; }
+    }
     const size_t lds = 131072 + (size_t)a.F * 4 + ((OP || QKV) ? 9 : 6) * (size_t)a.H * 4;   // b1, [b2 g2 e2], [bq], [bo g1 e1]
     static ppg::LdsLimit limit;
-    hipError_t e = limit.ensure(reinterpret_cast<const void*>(kern), lds);
+    hipError_t e = (which ? *which : limit).ensure(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, blocks, dim3(256), lds, s, a);
     e = hipGetLastError();

@@ -29,7 +29,9 @@ extern "C" {
 // token-split kernels take a ROW MAP (the 16-row blocks the step touches, of any items, one per wave) instead of a
 // contiguous row range, the attention launch takes the items' query tiles.  Rows are recomputed from the last block
 // boundary at or below an item's previous frontier; a recomputed row gives the same bits (the hidden chunks are
-// walked in a fixed order under a row map).
+// walked in a fixed order and summed in a fixed number of groups under a row map; attention re-bases a query's softmax
+// shift on that query's own sums alone): an item's outputs depend neither on the push cadence nor on what the other
+// items do (tests/test_gpu_stream_probe.py holds both, bit for bit).
 struct StreamItemMeta { int row0; int received_before; int count; int pad; };
 __global__ void stream_append_kernel(const StreamItemMeta* meta, const char* chunk, int nmax, int C, int R, int esz, char* feats) {
     const int b = blockIdx.y;
@@ -56,6 +58,7 @@ struct PpgStream {
     int* d_tickets = nullptr;     // one-pass split-hidden FFN: a counter per token tile, zero between launches (FfnArgs::tickets)
     size_t qk_bytes = 0, vt_bytes = 0, cache_off = 0, part_off = 0;
     int max_splits = 1;           // hidden splits of the FFN launches (a step's few rows cannot stream the weights through few CUs fast enough)
+    int ffn_groups = 1;           // the hidden GROUPS every FFN launch of this stream sums in; fixed for the life of the stream (below)
     std::vector<int> received, x_valid, o_valid;
     std::vector<char> finished;
     std::vector<int> map_scratch;
@@ -139,6 +142,19 @@ int ppg_stream_create_batch(PpgEngine* e, int batch, int max_frames, int feature
         const size_t tiles = (size_t)tb.max_blocks / 4 + 4;
         HIP_OK(hipMalloc(reinterpret_cast<void**>(&st->d_tickets), tiles * sizeof(int)));
         HIP_OK(hipMemset(st->d_tickets, 0, tiles * sizeof(int)));
+    }
+    // The split-hidden FFN sums the hidden chunks in GROUPS: every group from zero, the groups' sums in order, bias + residual
+    // last.  The number of groups is a property of the STREAM: chosen per step (as many splits as fill the chip), a step of
+    // many row blocks and a step of few summed in different orders, and the final rows of a frontier block -- recomputed by
+    // the next step, their X and K / V rows rewritten -- depended on the push cadence in the last bits
+    // (tests/test_gpu_stream_probe.py), against "a recomputed row gives the same bits".  The count is what the per-step rule
+    // gave a step of 16 frames per item (two row blocks each), the step the four-launch form is for; how the groups are
+    // spread over workgroups is still chosen per step (ppg_stream_push_batch) and does not change the arithmetic.
+    if (e->ffn_split && st->max_splits > 1) {
+        const int wgs = (2 * batch + 3) / 4;
+        int cap = e->ffn_split_max > 0 ? std::min(e->ffn_split_max, st->max_splits) : st->max_splits;
+        if (st->d_tickets) cap = std::min(cap, e->ffn_split_max > 0 ? 8 : 4);   // (one-pass form: the last workgroup sums the partial rows itself)
+        while (st->ffn_groups * 2 <= cap && wgs * st->ffn_groups * 2 <= e->num_cus) st->ffn_groups *= 2;
     }
     HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&st->staging), PpgStream::kSlots * tb.bytes, hipHostMallocDefault));
     for (hipEvent_t& ev : st->uploaded) HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -278,16 +294,16 @@ int ppg_stream_push_batch(PpgStream* st, const void* chunk, int nmax, const int*
     if (nmap[0] > 0) {
         const Rows t = rows_of(d_win, X, Xb, 0);
         LAUNCH_OK(ppg::launch_linear(prec, EPI_INCONV, 16, 1, inconv_args(e, t, xw), H / 256, s), "stream in-conv");
-        // hidden splits: as many workgroups per token tile as fill the chip (each streams its share of W1 / W2)
-        int ffn_splits = 1;
-        if (e->ffn_split) {
-            const int wgs = (nmap[0] + 3) / 4;
-            // (one-pass form: the tile's last workgroup sums the partial rows itself, 4 rows x <= 8 splits of loads in
-            // flight per wave; four splits keep that to two round trips)
-            int cap = e->ffn_split_max > 0 ? std::min(e->ffn_split_max, st->max_splits) : st->max_splits;
-            if (st->d_tickets) cap = std::min(cap, e->ffn_split_max > 0 ? 8 : 4);
-            while (ffn_splits * 2 <= cap && wgs * ffn_splits * 2 <= e->num_cus) ffn_splits *= 2;
-        }
+        // The stream's hidden groups (ffn_groups, fixed at creation) as one workgroup per group and token tile -- hidden
+        // splits, each streaming its share of W1 / W2: a step's few rows cannot stream the weights through few CUs fast
+        // enough -- while that is at most two rounds of workgroups on the chip.  A bigger step walks all groups in ONE
+        // workgroup per token tile, which closes its accumulator at the group boundaries and adds the sums in the reduce
+        // pass's order and applies LayerNorm-2 in that pass's arithmetic (FfnArgs::groups, ffn_closed_kernel): the same bits,
+        // no partial rows and no reduce launch (hidden 256; the hidden-512 kernel has no registers for the second accumulator
+        // and keeps the splits).  Measured: 64 x 160 frames 760 us against 845 us always spread.
+        const int ffn_wgs = (nmap[0] + 3) / 4;
+        const bool ffn_closed = st->ffn_groups > 1 && H == 256 && ffn_wgs * st->ffn_groups > 2 * e->num_cus;
+        const int ffn_splits = ffn_closed ? 1 : st->ffn_groups;
         // One launch per layer besides attention for BIG steps (round 5): out-projection + LayerNorm-1 + FFN + LayerNorm-2
         // + the NEXT layer's Q/K/V in the token-split fused kernel the one-shot forward uses for small batches, here under
         // the step's row map.  Its workgroups stream a whole layer's weights each (no hidden splits: a split would redo
@@ -314,6 +330,7 @@ int ppg_stream_push_batch(PpgStream* st, const void* chunk, int nmax, const int*
             LAUNCH_OK(ppg::launch_linear(prec, EPI_RESLN, H / 16, 1, outproj_ln_args(e, t, d, ao), 1, s), "stream out-proj+LN");
             FfnArgs a = ffn_args(e, t, d, ffn_splits, reinterpret_cast<float*>(base + st->part_off));
             a.tickets = ffn_splits > 1 ? st->d_tickets : nullptr;
+            if (ffn_closed) a.groups = st->ffn_groups;
             LAUNCH_OK(ppg::launch_ffn(prec, a, 1, s), "stream ffn");
         }
     }

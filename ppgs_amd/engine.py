@@ -1449,7 +1449,14 @@ class BatchedStream:
     the state the reference does not keep.  Item b is an utterance of its own (one window, <= 500 frames) with its
     own frontier: a push hands every item its own number of new frames (ragged, not aligned to anything, 0 = the
     item sits this step out) and ONE launch sequence advances them all.  Each item equals the causal forward of
-    its whole utterance, like :class:`Stream`."""
+    its whole utterance, like :class:`Stream`.
+
+    Invariants (tests/test_gpu_stream_probe.py holds them against float64 probes in all four precisions):
+    * emission: after every step item b has emitted max(received - 4, 0) frames, all of them once flushed;
+    * cadence: an item's outputs do not depend on how its frames were cut into pushes -- bit for bit, in the
+      default form and in the PPGS_AMD_STREAM_FUSED=2 form (the form, and the number of groups the FFN sums its
+      hidden chunks in, are properties of the stream, fixed when it is created);
+    * neighbours: an item's bits do not depend on what the other items of the batch are pushed, or when."""
 
     def __init__(self, engine, batch, max_frames, dtype=torch.float16):
         if dtype not in (torch.float16, torch.float32):
@@ -1521,7 +1528,11 @@ class LongStream:
     each a KV-cached Stream -- and emits the kept rows in frame order: the causal forward of the
     whole utterance as the reference computes it for T > 500, incrementally, with the windows'
     own look-ahead of 4 frames.  (For T <= 500 the reference uses ONE unpadded window, which is
-    what Stream reproduces; the regime cannot be switched once frames have been emitted.)"""
+    what Stream reproduces; the regime cannot be switched once frames have been emitted.)
+
+    Invariants (tests/test_gpu_stream_probe.py): never more than max(received - 4, 0) frames emitted before the
+    flush, all of them after it; at most two windows alive; and, as for Stream, the outputs do not depend on how
+    the frames were cut into pushes, bit for bit."""
 
     def __init__(self, engine, dtype=torch.float16):
         self.engine, self.dtype = engine, dtype

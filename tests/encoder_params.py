@@ -226,12 +226,12 @@ class Net:
     """One probe network (hidden, depth, causal) on one batch: the loud state dict, the features, the float64
     logits and the format costs."""
 
-    def __init__(self, hidden, depth, causal, valid=VALID, frames=FRAMES, state=None):
+    def __init__(self, hidden, depth, causal, valid=VALID, frames=FRAMES, state=None, feats=None):
         self.hidden, self.depth, self.causal = hidden, depth, bool(causal)
         self.valid, self.frames = tuple(valid), frames
         self.cin = GEOMETRY[hidden]
         self.state = loud_state(SEED, self.cin, hidden, depth) if state is None else state
-        self.feats = features(self.cin, len(self.valid), frames)
+        self.feats = features(self.cin, len(self.valid), frames) if feats is None else feats
         self.ref = reference64(self.state, self.feats, self.valid, self.causal)
         self.inside = A.inside(self.valid, frames)
         self._cost = {}
