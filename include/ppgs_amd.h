@@ -625,6 +625,76 @@ int ppg_recognize(int device, const float* ppg, int frames, int items, const int
                   void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Viterbi over a phoneme graph: the best path through a graph whose states each carry a phoneme -- pronunciation
+ * variants in parallel, substitution networks, a loop over the words of a lexicon, a chain with a phoneme twice.
+ * ppg_align, ppg_align_optional and ppg_recognize are special graphs of it.  Not in the reference.
+ *
+ * A graph has S states, 1 <= S <= PPG_VITERBI_MAX_STATES.  State n has a phoneme sym[n] in 0 .. 39, a weight stay[n]
+ * for remaining in it, an ordered list of in-arcs (src[j], w[j]), j = 0 .. deg(n) - 1, deg(n) <= PPG_VITERBI_MAX_DEGREE,
+ * and weights initial[n] and final[n].  Every weight is finite or -inf.  An arc n -> n is legal: it leaves the state and
+ * enters it again, so it opens a new run; parallel arcs are legal too.  For one utterance P (40, T), T >= 1:
+ *   e[t, n] = logp[t][sym[n]]                                   the prepared frame of ppg_align, the same kernel
+ *   D[0, n] = e[0, n] + initial[n]
+ *   t > 0:    best = D[t-1, n] + stay[n], from = 0
+ *             for j = 0 .. deg(n)-1 in list order:  c = D[t-1, src[j]] + w[j];  if c > best: best = c, from = j + 1
+ *             D[t, n] = e[t, n] + best                          fp32, one addition per candidate, in order of t
+ *   end:      F[n] = D[T-1, n] + final[n];  last = the first n with the largest F (strict >, ascending);  total = F[last]
+ * Comparisons only: staying wins ties, then the arc listed first.  -inf + finite = -inf and -inf > -inf is false, so a
+ * state nothing reaches never gives NaN.  If total = -inf there is no path: runs = 0 and nothing else is written.
+ * The trace-back from `last` gives one state per frame.  A run opens at frame 0 and at every frame whose `from` != 0
+ * (two runs of one state follow each other through an arc n -> n).  Per run r < R:
+ *   states[r], phonemes[r] = sym[states[r]];  starts[r] its first frame, starts[0] = 0, starts[R] = T;  runs = R
+ *   score[r], gop[r]  as ppg_recognize and ppg_align compute them (the same code on the runs as a transcript)
+ *
+ * Several graphs travel packed in one call:
+ *   graphs, n_states, n_arcs : host integers: the graphs, and the states and arcs of all of them together
+ *   max_states      : host integer, 1 .. PPG_VITERBI_MAX_STATES: no graph of the call has more states
+ *   state_begin     : device int32[graphs + 1]: the states of graph g are state_begin[g] .. state_begin[g + 1] - 1
+ *   state_phonemes  : device int32[n_states]
+ *   stay, initial, final_ : device fp32[n_states]
+ *   arc_begin       : device int32[n_states + 1]: the in-arcs of state n (an index over all states) are arc_begin[n] ..
+ *                     arc_begin[n + 1] - 1
+ *   sources         : device int32[n_arcs]: the state an arc comes from, counted inside its own graph
+ *   weights         : device fp32[n_arcs]      (sources and weights may be NULL if n_arcs is 0)
+ *   which           : device int32[items], the graph of every item; NULL means graph 0 for all
+ *   ppg, lengths    : as for ppg_align
+ *   states, phonemes : device int32 (items, frames): entries 0 .. R-1 of item b are written
+ *   starts          : device int32 (items, frames + 1): entries 0 .. R are written
+ *   runs, total     : device int32[items], fp32[items]
+ *   score, gop      : device fp32 (items, frames): entries 0 .. R-1 are written; gop may be NULL
+ *   workspace       : device memory, 16-byte aligned, at least ppg_viterbi_workspace_bytes(items, frames, max_states)
+ *                     bytes: five blocks, each 256-byte aligned: the prepared frames (176 B per frame), the back-pointers
+ *                     (one byte per state and frame: 64 per frame if max_states <= 64, else max_states rounded up to
+ *                     256), one int32 label per frame, the end state of every item, and the verdict on every graph
+ * The entry does not read device memory, so the device checks the graphs, once per graph: a graph is refused if
+ * state_begin or arc_begin decreases or leaves its array, S is outside [1, max_states], a degree exceeds
+ * PPG_VITERBI_MAX_DEGREE, the graph has more than PPG_VITERBI_MAX_ARCS arcs, a source is outside [0, S), a phoneme
+ * outside 0 .. 39, or a weight is NaN or +inf; every test is made before the read that depends on it.  An item whose
+ * graph was refused, whose `which` is outside [0, graphs) or whose length is outside [1, frames] gets total = NaN and
+ * runs = 0 and nothing else.  No input makes a kernel read or write outside its buffers.
+ * Kernel launches on `stream` only: no allocation, synchronisation or copy; every byte a kernel reads was written by an
+ * earlier kernel of the same call, so the workspace needs no clearing.  Calls with workspaces of their own may run
+ * concurrently on several streams.  A batch equals its singles bit for bit.
+ * PPG_EINVAL, with nothing launched, for a NULL required pointer, an unaligned pointer, an unaligned or short workspace,
+ * graphs, n_states, n_arcs or max_states that cannot be (n_states < graphs, n_states > graphs * max_states, n_arcs >
+ * graphs * PPG_VITERBI_MAX_ARCS), or more than PPG_VITERBI_MAX_FRAMES frames, PPG_VITERBI_MAX_ITEMS items or
+ * PPG_VITERBI_MAX_GRAPHS graphs (ppg_viterbi_workspace_bytes, which is host-only, returns 0 for such arguments).
+ */
+#define PPG_VITERBI_MAX_STATES 1024
+#define PPG_VITERBI_MAX_ARCS   32768         /* per graph */
+#define PPG_VITERBI_MAX_DEGREE 255           /* a back-pointer is one byte: 0 stays, j + 1 is in-arc j */
+#define PPG_VITERBI_MAX_FRAMES 262144        /* = PPG_RECOGNIZE_MAX_FRAMES */
+#define PPG_VITERBI_MAX_ITEMS  65535
+#define PPG_VITERBI_MAX_GRAPHS 65535
+size_t ppg_viterbi_workspace_bytes(int items, int frames, int max_states);
+int ppg_viterbi(int device, const float* ppg, int frames, int items, const int32_t* lengths,
+                int graphs, int n_states, int n_arcs, int max_states, const int32_t* state_begin,
+                const int32_t* state_phonemes, const float* stay, const float* initial, const float* final_,
+                const int32_t* arc_begin, const int32_t* sources, const float* weights, const int32_t* which,
+                int32_t* states, int32_t* phonemes, int32_t* starts, int32_t* runs, float* total, float* score,
+                float* gop, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Phrase search: where in a recording is a phoneme sequence said, and how well (keyword spotting on posteriorgrams).
  * ppg_align pins its transcript to frame 0 and frame T-1; here the match may start and end at any frame.  Not in the
  * reference.

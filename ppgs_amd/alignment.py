@@ -48,6 +48,30 @@ phonemes, it is `forced(ppg, s)` bit for bit, and with A = 0 it is `decode` wher
     said = ppgs_amd.alignment.recognize(ppg, transitions=A, initial=initial, final=final)
     for name, start, end, score, gop in ppgs_amd.alignment.segments(said): ...
 
+Graphs (`viterbi`, ppg_viterbi): `forced` takes one sequence and `recognize` the 40 phonemes themselves; pronunciation
+variants ("either" is iy dh er or ay dh er), substitution networks, a loop over the words of a lexicon and a chain with
+a phoneme twice are all the best path through a graph whose states each carry a phoneme.  A Graph has S <= 1024 states;
+state n has a phoneme sym[n], a weight stay[n], an ordered list of at most 255 in-arcs (src[j], w[j]) and weights
+initial[n] and final[n], every weight finite or -inf:
+
+    e[t, n] = the log-posterior above, of phoneme sym[n]
+    D[0, n] = e[0, n] + initial[n]
+    best = D[t-1, n] + stay[n], from = 0
+    for j in list order:  c = D[t-1, src[j]] + w[j];  if c > best: best = c, from = j + 1
+    D[t, n] = e[t, n] + best                                     fp32, one addition per candidate, in order of t
+    F[n] = D[T-1, n] + final[n];  last = the first n with the largest F;  total = F[last]
+
+Comparisons only: staying wins ties, then the arc listed first.  The trace-back from `last` gives a state per frame; a
+run opens at frame 0 and wherever `from` != 0, so an arc n -> n opens a second run of n.  The result is a Path: per run
+its state, its phoneme, its first frame, and `forced`'s score and gop.  `forced`, `forced(optional=)` and `recognize`
+are special graphs (`chain_graph`, `model_graph`) and `viterbi` equals them bit for bit there.
+
+    graph, word_of, variant_of = ppgs_amd.alignment.pronunciations([[['dh', 'ah'], ['dh', 'iy']], [['k', 'ae', 't']]])
+    path = ppgs_amd.alignment.viterbi(ppg, graph)
+    said = [variant_of[n] for n in path.states.tolist()]                       # which variant each run belongs to
+    graph, word_of = ppgs_amd.alignment.word_loop({'yes': [['y', 'eh', 's']], 'no': [['n', 'ow']]}, penalty=2.)
+Not here: a streaming form, states that emit nothing, N-best lists, minimum durations, more than 1024 states.
+
 Optional phonemes (`forced(..., optional=flags)`, ppg_align_optional): a speaker pauses between words wherever they
 like, and drops a final consonant or a schwa.  flags[n] lets the path leave phoneme n out:
 
@@ -145,10 +169,16 @@ RECOGNIZE_MAX_FRAMES = engine.RECOGNIZE_MAX_FRAMES
 SEARCH_MAX_FRAMES = engine.SEARCH_MAX_FRAMES
 SEARCH_MAX_PHONEMES = engine.SEARCH_MAX_PHONEMES
 SEARCH_MAX_HITS = engine.SEARCH_MAX_HITS
+VITERBI_MAX_FRAMES = engine.VITERBI_MAX_FRAMES
+VITERBI_MAX_STATES = engine.VITERBI_MAX_STATES
+VITERBI_MAX_ARCS = engine.VITERBI_MAX_ARCS
+VITERBI_MAX_DEGREE = engine.VITERBI_MAX_DEGREE
 
 Alignment = collections.namedtuple('Alignment', ['phonemes', 'starts', 'total', 'score', 'gop'])
 Decoding = collections.namedtuple('Decoding', ['phonemes', 'starts'])
 Recognition = collections.namedtuple('Recognition', Alignment._fields)
+Graph = collections.namedtuple('Graph', ['phonemes', 'stay', 'offsets', 'sources', 'weights', 'initial', 'final'])
+Path = collections.namedtuple('Path', ['states', 'phonemes', 'starts', 'total', 'score', 'gop'])
 Hits = collections.namedtuple('Hits', ['phonemes', 'begin', 'end', 'total', 'mean', 'count', 'curve'])
 Runs = collections.namedtuple('Runs', ['phonemes', 'begin', 'end', 'score', 'gop', 'count', 'total', 'forced'])
 
@@ -539,6 +569,329 @@ def recognize(ppg, lengths=None, transitions=None, initial=None, final=None, pen
     return Recognition(
         [phonemes[b, :r] for b, r in enumerate(runs)], [starts[b, :r + 1] for b, r in enumerate(runs)], total,
         [score[b, :r] for b, r in enumerate(runs)], [below[b, :r] for b, r in enumerate(runs)] if gop else None)
+
+
+def _weight(value, what):
+    """One weight of a graph as a float: finite or -inf."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise ValueError(f'{what}: a weight must be a number, got {value!r}')
+    value = float(value)
+    if math.isnan(value) or value == math.inf:
+        raise ValueError(f'{what}: a weight is finite or -inf, got {value}')
+    return value
+
+
+def _state_weights(values, count, default, name):
+    """A weight per state from None (the default for all), one number (for all), or a list or tensor of `count`."""
+    if values is None:
+        return [default] * count
+    if isinstance(values, (int, float)) and not isinstance(values, bool):
+        return [_weight(values, name)] * count
+    if torch.is_tensor(values):
+        if values.dim() != 1 or values.is_complex() or values.dtype == torch.bool:
+            raise ValueError(f'{name} must be a one-dimensional tensor of weights, got {tuple(values.shape)} '
+                             f'{values.dtype}')
+        values = values.detach().cpu().to(torch.float64).tolist()
+    if not isinstance(values, (list, tuple)) or len(values) != count:
+        raise ValueError(f'{name} must be a number or hold one weight per state ({count})')
+    return [_weight(value, f'{name} of state {n}') for n, value in enumerate(values)]
+
+
+def _assemble(symbols, stay, arcs_into, initial, final):
+    """A Graph from checked host lists: arcs_into[n] is the ordered list of (source, weight) into state n."""
+    count = len(symbols)
+    if not 1 <= count <= VITERBI_MAX_STATES:
+        raise ValueError(f'a graph has 1 to {VITERBI_MAX_STATES} states, got {count}')
+    offsets = [0]
+    for n, into in enumerate(arcs_into):
+        if len(into) > VITERBI_MAX_DEGREE:
+            raise ValueError(f'state {n} has {len(into)} arcs coming in, at most {VITERBI_MAX_DEGREE}: a back-pointer '
+                             f'is one byte')
+        offsets.append(offsets[-1] + len(into))
+    if offsets[-1] > VITERBI_MAX_ARCS:
+        raise ValueError(f'a graph has at most {VITERBI_MAX_ARCS} arcs, got {offsets[-1]}')
+    return Graph(
+        torch.tensor(symbols, dtype=torch.int32), torch.tensor(stay, dtype=torch.float32),
+        torch.tensor(offsets, dtype=torch.int32),
+        torch.tensor([source for into in arcs_into for source, _ in into], dtype=torch.int32),
+        torch.tensor([weight for into in arcs_into for _, weight in into], dtype=torch.float32),
+        torch.tensor(initial, dtype=torch.float32), torch.tensor(final, dtype=torch.float32))
+
+
+def graph(phonemes, arcs, stay=0., initial=None, final=None):
+    """A Graph for `viterbi` from its states and arcs.  State n carries phonemes[n] (names or indices, 1 to 1024 of
+    them); `arcs` is a list of (source, target, weight): the path may go from `source` at one frame to `target` at the
+    next for `weight`.  The arcs into a state keep their listed order, which decides ties (the module's text); at most
+    255 may enter one state and a graph has at most 32768.  An arc n -> n is legal and opens a new run of n; parallel
+    arcs are legal.  `stay`, `initial` and `final` are a number for every state or one weight per state (a list or a
+    tensor); initial and final None weigh nothing: the path may begin and end in any state.  Every weight is finite or
+    -inf.  Raises ValueError, naming the state, on everything the device would refuse.  Host only."""
+    symbols = _sequence(phonemes)
+    count = len(symbols)
+    if not 1 <= count <= VITERBI_MAX_STATES:
+        raise ValueError(f'a graph has 1 to {VITERBI_MAX_STATES} states, got {count}')
+    if isinstance(arcs, (str, bytes)) or not isinstance(arcs, (list, tuple)):
+        raise ValueError(f'arcs must be a list of (source, target, weight), got {type(arcs).__name__}')
+    into = [[] for _ in range(count)]
+    for index, arc in enumerate(arcs):
+        if not isinstance(arc, (list, tuple)) or len(arc) != 3:
+            raise ValueError(f'arc {index} must be (source, target, weight), got {arc!r}')
+        source, target, weight = arc
+        for name, state in (('source', source), ('target', target)):
+            if isinstance(state, bool) or not isinstance(state, int) or not 0 <= state < count:
+                raise ValueError(f'arc {index}: the {name} {state!r} is not a state in [0, {count - 1}]')
+        into[target].append((source, _weight(weight, f'arc {index} into state {target}')))
+    return _assemble(symbols, _state_weights(stay, count, 0., 'stay'), into,
+                     _state_weights(initial, count, 0., 'initial'), _state_weights(final, count, 0., 'final'))
+
+
+def chain_graph(phonemes, optional=None):
+    """The left-to-right chain over a phoneme sequence s as a Graph, repeated phonemes allowed (a state is a position,
+    not a phoneme): state n carries s[n], staying and advancing weigh 0, the path begins in state 0 and ends in state
+    N - 1.  `viterbi` under it is `forced(ppg, s)` bit for bit.  With `optional` (flags as `forced` takes them for one
+    sequence) it is the topology of `forced(ppg, s, optional=)`: state n takes the arcs advance (from n - 1), then skip
+    (from n - 2 if flags[n - 1]); the path may also begin in state 1 if flags[0] and end in state N - 2 if
+    flags[N - 1].  The states a path does not visit are the phonemes left out.  Host only."""
+    symbols = _sequence(phonemes)
+    count = len(symbols)
+    if not 1 <= count <= VITERBI_MAX_STATES:
+        raise ValueError(f'a chain takes 1 to {VITERBI_MAX_STATES} phonemes, got {count}')
+    flags = [False] * count if optional is None else _flags(optional, [symbols], False, [count])[0]
+    into = [[] for _ in range(count)]
+    for n in range(1, count):
+        into[n].append((n - 1, 0.))
+        if n >= 2 and flags[n - 1]:
+            into[n].append((n - 2, 0.))
+    initial, final = [-math.inf] * count, [-math.inf] * count
+    initial[0] = final[count - 1] = 0.
+    if flags[0]:
+        initial[1] = 0.                                        # (some phoneme is mandatory, so there is a state 1)
+    if flags[count - 1]:
+        final[count - 2] = 0.
+    return _assemble(symbols, [0.] * count, into, initial, final)
+
+
+def model_graph(transitions, initial=None, final=None):
+    """The model of `recognize` as a Graph of 40 states: state q carries phoneme q, stay[q] = transitions[q, q], and
+    its arcs come from every p != q in ascending p with transitions[p, q].  `viterbi` under it is `recognize` bit for
+    bit.  Host only."""
+    count = len(PHONEMES)
+    matrix = _weights(transitions, (count, count), 'transitions').cpu().tolist()
+    first = [0.] * count if initial is None else _weights(initial, (count,), 'initial').cpu().tolist()
+    last = [0.] * count if final is None else _weights(final, (count,), 'final').cpu().tolist()
+    into = [[(p, matrix[p][q]) for p in range(count) if p != q] for q in range(count)]
+    return _assemble(list(range(count)), [matrix[q][q] for q in range(count)], into, first, last)
+
+
+def _variants(word, what):
+    """The pronunciations of one word: a non-empty list of non-empty index lists."""
+    if isinstance(word, (str, bytes)) or not isinstance(word, (list, tuple)) or len(word) < 1:
+        raise ValueError(f'{what} takes a non-empty list of pronunciations, each a list of phonemes')
+    out = []
+    for variant in word:
+        if not torch.is_tensor(variant) and not isinstance(variant, (list, tuple)):
+            raise ValueError(f'{what}: a pronunciation is a list of phonemes, got {variant!r}')
+        sequence = _sequence(variant)
+        if not sequence:
+            raise ValueError(f'{what} has a pronunciation without phonemes')
+        out.append(sequence)
+    return out
+
+
+def pronunciations(words, silence=True):
+    """A transcript whose words have alternative pronunciations, for `viterbi`: (graph, word_of, variant_of).
+
+    `words` is a list of words, each a list of alternative phoneme sequences ("either": [['iy', 'dh', 'er'], ['ay',
+    'dh', 'er']]).  The variants of a word stand in parallel, every variant of a word joined to every variant of the
+    next; with `silence` an optional '<silent>' state stands before the first word, between words and after the last,
+    as `transcript` places it.  A word's first states take the arc from the silence before them first, then those from
+    the last states of the word before, in the order of its variants.  All weights are 0: the total is the largest
+    total `forced(..., optional=)` gives over all combinations of variants.  word_of[n] and variant_of[n] are the word
+    and its variant state n belongs to, -1 for the silences: read the words' times and the variants chosen off
+    `Path.states`.  Host only."""
+    if isinstance(words, (str, bytes)) or not isinstance(words, (list, tuple)) or len(words) < 1:
+        raise ValueError('pronunciations takes a non-empty list of words, each a list of alternative phoneme sequences')
+    quiet = PHONEME_TO_INDEX_MAPPING['<silent>']
+    symbols, into, word_of, variant_of = [], [], [], []
+
+    def state(symbol, word, variant, sources):
+        symbols.append(symbol)
+        into.append([(source, 0.) for source in sources])
+        word_of.append(word)
+        variant_of.append(variant)
+        return len(symbols) - 1
+    begins, ends = [], []                                      # where the path may begin; the last states so far
+    for index, word in enumerate(words):
+        before = list(ends)
+        if silence:
+            before = [state(quiet, -1, -1, ends)] + before     # the pause first: advance before skip
+        if index == 0:
+            begins = list(before)
+        ends = []
+        for number, sequence in enumerate(_variants(word, f'word {index}')):
+            sources = before
+            for symbol in sequence:
+                at = state(symbol, index, number, sources)
+                if sources is before and index == 0:
+                    begins.append(at)
+                sources = [at]
+            ends.append(at)
+    if silence:
+        ends = ends + [state(quiet, -1, -1, ends)]
+    count = len(symbols)
+    initial, final = [-math.inf] * count, [-math.inf] * count
+    for n in begins:
+        initial[n] = 0.
+    for n in ends:
+        final[n] = 0.
+    return _assemble(symbols, [0.] * count, into, initial, final), word_of, variant_of
+
+
+def word_loop(lexicon, penalty=0., silence=True):
+    """A loop over the words of a lexicon, for `viterbi`: (graph, word_of).  `lexicon` is a dict, or a list of pairs,
+    of word -> pronunciations (a list of alternative phoneme sequences).  Any word may follow any word; entering a
+    word, also the first, costs `penalty` (>= 0, finite); with `silence` one '<silent>' state may be passed between
+    words, before the first and after the last.  Every pronunciation is a chain of its own; its first state takes the
+    arc from the silence first, then one from the last state of every pronunciation, in lexicon order.  word_of[n] is
+    the index of state n's word in the lexicon's order, -1 for the silence: a word is said wherever `Path.states`
+    enters a first state.  The last states of all pronunciations (the word ends) enter every first state, so their
+    number is bounded by the degree limit, and their square by the limit on arcs; a lexicon beyond either is refused.
+    The limit on arcs comes first, at about 180 word ends (E ends enter E words: E * (E + 1) arcs of 32768), so no word
+    loop has a state of the largest degree, 255: only `graph` builds one.  Host only."""
+    if isinstance(penalty, bool) or not isinstance(penalty, (int, float)) or not 0 <= penalty < math.inf:
+        raise ValueError(f'a word penalty must be a finite number >= 0, got {penalty!r}')
+    pairs = list(lexicon.items()) if isinstance(lexicon, dict) else lexicon
+    if isinstance(pairs, (str, bytes)) or not isinstance(pairs, (list, tuple)) or len(pairs) < 1:
+        raise ValueError('a word loop takes a non-empty lexicon: a dict or a list of (word, pronunciations)')
+    chains = []
+    for index, pair in enumerate(pairs):
+        if not isinstance(pair, (list, tuple)) or len(pair) != 2:
+            raise ValueError(f'lexicon entry {index} must be (word, pronunciations), got {pair!r}')
+        chains.extend((index, sequence) for sequence in _variants(pair[1], f'word {pair[0]!r}'))
+    allowed = VITERBI_MAX_DEGREE - (1 if silence else 0)
+    if len(chains) > allowed:
+        raise ValueError(f'the lexicon has {len(chains)} word ends (pronunciations), at most {allowed} are allowed: '
+                         f'each enters every word, and a state takes {VITERBI_MAX_DEGREE} arcs')
+    cost = -float(penalty)
+    quiet = PHONEME_TO_INDEX_MAPPING['<silent>']
+    base = 1 if silence else 0
+    firsts, lasts, at = [], [], base
+    for _, sequence in chains:
+        firsts.append(at)
+        at += len(sequence)
+        lasts.append(at - 1)
+    if at > VITERBI_MAX_STATES:
+        raise ValueError(f'the lexicon takes {at} states, at most {VITERBI_MAX_STATES}')
+    entering = ([(0, cost)] if silence else []) + [(last, cost) for last in lasts]
+    arcs = len(entering) * len(chains) + (len(lasts) if silence else 0) + at - base - len(chains)
+    if arcs > VITERBI_MAX_ARCS:
+        raise ValueError(f'the lexicon takes {arcs} arcs, at most {VITERBI_MAX_ARCS}: {len(chains)} word ends enter '
+                         f'{len(chains)} words each')
+    symbols, into, word_of = [], [], []
+    initial, final = [], []
+    if silence:
+        symbols.append(quiet); into.append([(last, 0.) for last in lasts]); word_of.append(-1)
+        initial.append(0.); final.append(0.)
+    for index, sequence in chains:
+        for position, symbol in enumerate(sequence):
+            symbols.append(symbol)
+            into.append(list(entering) if position == 0 else [(len(symbols) - 2, 0.)])
+            word_of.append(index)
+            initial.append(cost if position == 0 else -math.inf)
+            final.append(0. if position == len(sequence) - 1 else -math.inf)
+    return _assemble(symbols, [0.] * len(symbols), into, initial, final), word_of
+
+
+def _checked_graph(value):
+    """A Graph as `viterbi` takes it: the builders' own, or one made by hand, which is checked here as the device
+    would check it (vectorised: no loop over states)."""
+    if not isinstance(value, Graph):
+        raise ValueError(f'viterbi takes a Graph (graph, chain_graph, model_graph, pronunciations, word_loop), got '
+                         f'{type(value).__name__}')
+    for name, tensor in zip(Graph._fields, value):
+        if not torch.is_tensor(tensor) or tensor.dim() != 1 or tensor.is_cuda:
+            raise ValueError(f'Graph.{name} must be a one-dimensional CPU tensor')
+    count, arcs = value.phonemes.shape[0], value.sources.shape[0]
+    if not 1 <= count <= VITERBI_MAX_STATES:
+        raise ValueError(f'a graph has 1 to {VITERBI_MAX_STATES} states, got {count}')
+    if arcs > VITERBI_MAX_ARCS:
+        raise ValueError(f'a graph has at most {VITERBI_MAX_ARCS} arcs, got {arcs}')
+    for name, size in (('stay', count), ('initial', count), ('final', count), ('offsets', count + 1), ('weights', arcs)):
+        if getattr(value, name).shape[0] != size:
+            raise ValueError(f'Graph.{name} has {getattr(value, name).shape[0]} entries, {size} expected')
+    for name in ('phonemes', 'offsets', 'sources'):
+        tensor = getattr(value, name)
+        if tensor.is_floating_point() or tensor.is_complex() or tensor.dtype == torch.bool:
+            raise ValueError(f'Graph.{name} must be an integer tensor, got {tensor.dtype}')
+    offsets = value.offsets.to(torch.int64)
+    degrees = offsets[1:] - offsets[:-1]
+    if int(offsets[0]) != 0 or int(offsets[-1]) != arcs or bool((degrees < 0).any()):
+        raise ValueError('Graph.offsets must rise from 0 to the number of arcs')
+    if bool((degrees > VITERBI_MAX_DEGREE).any()):
+        raise ValueError(f'state {int(degrees.argmax())} has {int(degrees.max())} arcs coming in, at most '
+                         f'{VITERBI_MAX_DEGREE}')
+    if bool(((value.phonemes < 0) | (value.phonemes >= len(PHONEMES))).any()):
+        raise ValueError(f'a phoneme index of the graph is outside [0, {len(PHONEMES) - 1}]')
+    if bool(((value.sources < 0) | (value.sources >= count)).any()):
+        raise ValueError(f'a source of the graph is not a state in [0, {count - 1}]')
+    for name in ('stay', 'weights', 'initial', 'final'):
+        tensor = getattr(value, name)
+        if not tensor.is_floating_point() or bool((torch.isnan(tensor) | (tensor == math.inf)).any()):
+            raise ValueError(f'Graph.{name} must hold weights, each finite or -inf')
+    return value
+
+
+def viterbi(ppg, graph, lengths=None, gop=True):
+    """The best path of `ppg` through a graph of phoneme states (see the module's text): Path(states, phonemes,
+    starts, total, score, gop), one entry per run of the path.
+
+    `ppg` is (40, T) or a batch (B, 40, T) padded to the longest item with `lengths` per item (the padding is never
+    read), up to 262144 frames.  `graph` is a Graph (`graph`, `chain_graph`, `model_graph`, `pronunciations`,
+    `word_loop`) for every item, or for a batch a list of B of them (the same object may stand for several items and
+    travels once).  One utterance returns device tensors: states and phonemes (R,) int32, starts (R + 1,) int32, total
+    0-d, score and gop (R,) fp32; a batch returns lists of B such tensors and total (B,), as `recognize` does, and
+    equals its single calls bit for bit.  A run is a stretch of frames in one state; a path that leaves a state through
+    an arc back into it opens a new run of that state.  gop=False skips that sum and returns None for it.  An utterance
+    that no path fits has no runs, starts = [0] and total = -inf.  `segments` and `frame_labels` take the result as
+    they take an Alignment."""
+    batched, batch, frames = _ppg(ppg, VITERBI_MAX_FRAMES, 'viterbi')
+    if not batched and lengths is not None:
+        raise ValueError('lengths go with a batch: slice a single PPG instead')
+    lengths = _lengths(lengths, batch, frames)
+    which = None
+    if isinstance(graph, (list, tuple)) and not isinstance(graph, Graph):
+        if not batched or len(graph) != batch:
+            raise ValueError(f'a list of graphs goes with a batch of as many items, got {len(graph)} for {batch}')
+        packed, places, which = [], {}, []
+        for value in graph:
+            if id(value) not in places:
+                places[id(value)] = len(packed)
+                packed.append(_checked_graph(value))
+            which.append(places[id(value)])
+    else:
+        packed = [_checked_graph(graph)]
+    counts = [value.phonemes.shape[0] for value in packed]
+    state_begin = torch.tensor([0] + counts, dtype=torch.int64).cumsum(0)
+    arc_base = torch.tensor([0] + [value.sources.shape[0] for value in packed], dtype=torch.int64).cumsum(0)
+    arc_begin = torch.cat([value.offsets[:-1].to(torch.int64) + arc_base[g] for g, value in enumerate(packed)] +
+                          [arc_base[-1:]])
+
+    def joined(name):
+        return torch.cat([getattr(value, name) for value in packed])
+    device = core.device_for(None, ppg)
+    x = ppg.to(device)
+    states, phonemes, starts, runs, total, score, below = engine.viterbi_items(
+        x if batched else x[None], lengths, state_begin, joined('phonemes'), joined('stay'), joined('initial'),
+        joined('final'), arc_begin, joined('sources'), joined('weights'), which, max(counts), gop)
+    runs = runs.tolist()
+    if not batched:
+        r = runs[0]
+        return Path(states[0, :r], phonemes[0, :r], starts[0, :r + 1], total[0], score[0, :r],
+                    below[0, :r] if gop else None)
+    return Path(
+        [states[b, :r] for b, r in enumerate(runs)], [phonemes[b, :r] for b, r in enumerate(runs)],
+        [starts[b, :r + 1] for b, r in enumerate(runs)], total, [score[b, :r] for b, r in enumerate(runs)],
+        [below[b, :r] for b, r in enumerate(runs)] if gop else None)
 
 
 def _queries(phonemes):

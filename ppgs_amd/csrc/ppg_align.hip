@@ -2,7 +2,8 @@
 // run-length decode, on the device.  Phrase search (ppg_search) stands at the end, and after
 // it the same search carried across the pushes of a stream (ppg_search_stream_*), then the phoneme
 // recogniser, the best path through all 40 phonemes under a transition model (ppg_recognize), and last
-// that recogniser carried across the pushes of a stream (ppg_recognize_stream_*).
+// that recogniser carried across the pushes of a stream (ppg_recognize_stream_*).  The best path through a
+// graph of phoneme states (ppg_viterbi) follows the live recogniser.
 //
 //   e[t, n] = logf(min(max(P[s[n], t], 1e-8), 1 - 1e-8))                      (the clamp of ppg_distance)
 //   D[0, 0] = e[0, 0];  D[0, n > 0] = -inf
@@ -1526,6 +1527,413 @@ __global__ __launch_bounds__(64) void recognize_stream_reset(const int* __restri
     restart(heads + item, state_d + (size_t)item * 64, state_anc + (size_t)item * 64, threadIdx.x);
 }
 
+// ---- Viterbi over a phoneme graph (ppg_viterbi) ----
+//
+// The best path through a graph whose S <= 1024 states each carry a phoneme: state n has a weight stay[n], an ordered
+// list of in-arcs (src[j], w[j]), j < deg(n) <= 255, and weights initial[n] and final[n].
+//   e[t, n] = the prepared frame of align_prepare at sym[n]
+//   D[0, n] = e[0, n] + initial[n]
+//   best = D[t-1, n] + stay[n], from = 0;  for j in list order: c = D[t-1, src[j]] + w[j]; if c > best: best = c, from = j+1
+//   D[t, n] = e[t, n] + best                                   fp32, one addition per candidate, in order of t
+//   F[n] = D[T-1, n] + final[n];  last = the first n with the largest F (strict >, ascending);  total = F[last]
+// A run opens at frame 0 and at every frame of the trace-back whose `from` != 0.  Four kernels beside align_prepare and
+// align_score, which are shared:
+//   viterbi_check      one wave per GRAPH of the call, not per item: every index and weight of the packed graphs is
+//                      tested, each before the read that depends on it, and a verdict is left.  The kernels below trust
+//                      a graph with a good verdict and touch no other.
+//   viterbi_programme  one wave per utterance.  A state's predecessors are other lanes' states, so D of frame t-1 is read
+//                      by index from LDS (two buffers of 1024 floats, one barrier per frame), and what a state keeps
+//                      (phoneme, first arc and degree in one word, the stay weight) stands in LDS beside it: nothing of
+//                      a state lives in registers across frames, so 1024 states cost no more registers than 64.  If the
+//                      call's graphs have at most 64 states, lane n takes state n; else a frame is ceil(S / 256) passes
+//                      in which lane l takes the four neighbouring states 4 l .. 4 l + 3 of the pass, whose words move
+//                      as 16-byte pieces.  The arcs, 8 bytes each (source, weight), are copied to LDS once if the graph
+//                      has at most `held` of them, else they come from the caller's arrays (L2) every frame.  The first
+//                      VLEAD arcs of a lane's states are taken in lock step, so their LDS reads are in flight together
+//                      (a chain ends there); the rest state by state, four arcs and then eight at a time.  One
+//                      back-pointer byte per state and frame, the ordinal `from`: a lane's four are one dword, 256
+//                      contiguous bytes a wave.
+//   viterbi_traceback  one wave per utterance: back-pointer rows come through LDS 16 KiB at a time, the next refill in
+//                      flight, and of a row only what the graph's own passes wrote, whatever the call's largest graph
+//                      is; the walk is wave-uniform.  An ordinal becomes its source state through the arcs' sources,
+//                      held in LDS on the same condition, and only at the frames where the path changes state.  Frame
+//                      t's label is its state with one more bit that flips wherever a run opens, so two neighbouring
+//                      labels differ exactly there, also for two runs of one state.
+//   viterbi_runs       one wave per utterance: decode_runs' run compression (open_runs) on that label row, then the
+//                      states and their phonemes.
+// align_score then scores the runs as a transcript of `runs` phonemes among at most `frames`.
+
+constexpr int VSTATES = PPG_VITERBI_MAX_STATES;
+constexpr int VLEAD = 2;                      // arcs per state taken in lock step over a lane's slots
+constexpr int VAHEAD = 8;                     // arcs of a state read ahead of their compares, past its first six
+constexpr int VHELD = 4096;                   // arcs of a graph the programme keeps in LDS (32 KiB) at most
+constexpr int VROWS_VEC = 1024;               // 16-byte pieces per refill of the trace-back: 16 KiB
+constexpr int VPARITY = 1 << 16;              // the bit of a label that flips where a run opens
+static_assert(VSTATES % 256 == 0 && VSTATES <= VPARITY, "a label holds a state below its parity bit");
+static_assert(PPG_VITERBI_MAX_ARCS <= 1 << 15 && PPG_VITERBI_MAX_DEGREE == 255, "16 bits of arc index, 8 of degree");
+
+struct ViterbiLayout {
+    size_t logp, back, labels, ends, verdict, bytes;           // byte offsets into the workspace
+};
+
+// back-pointer bytes of one frame, a byte per state: whole passes of the programme over the call's largest graph
+__host__ __device__ inline int viterbi_row(int max_states) { return max_states <= 64 ? 64 : (max_states + 255) & ~255; }
+
+// back-pointer bytes of one utterance
+__host__ __device__ inline size_t viterbi_back_bytes(int frames, int max_states) {
+    return (size_t)frames * viterbi_row(max_states);
+}
+
+// (65535 items of 262144 frames and 1024 states are 1.8e13 bytes: inside a size_t)
+inline ViterbiLayout viterbi_layout(int items, int frames, int max_states) {
+    ViterbiLayout w{};
+    size_t at = 0;
+    w.logp = at; at += prepared_bytes(items, frames);
+    w.back = at; at = align256(at + (size_t)items * viterbi_back_bytes(frames, max_states));
+    w.labels = at; at = align256(at + (size_t)items * frames * sizeof(int));
+    w.ends = at; at = align256(at + (size_t)items * sizeof(int));
+    w.verdict = at; at = align256(at + (size_t)PPG_VITERBI_MAX_GRAPHS * sizeof(int));
+    w.bytes = at;
+    return w;
+}
+
+// a weight is finite or -inf
+__device__ __forceinline__ bool bad_weight(float w) { return w != w || w == INFINITY; }
+
+// grid (graphs), 64 threads: lane = state of the current 64.  Every test stands before the read that depends on it.
+__global__ __launch_bounds__(64) void viterbi_check(int n_states, int n_arcs, int max_states,
+                                                     const int* __restrict__ state_begin,
+                                                     const int* __restrict__ phonemes, const float* __restrict__ stay,
+                                                     const float* __restrict__ initial,
+                                                     const float* __restrict__ final_,
+                                                     const int* __restrict__ arc_begin,
+                                                     const int* __restrict__ sources,
+                                                     const float* __restrict__ weights, int* __restrict__ verdict)
+{
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const int first = state_begin[g], end = state_begin[g + 1];
+    bool fine = first >= 0 && end <= n_states && first < end && end - first <= max_states;
+    if (fine) {                                                // (uniform)
+        const int S = end - first;
+        bool bad = false;
+        for (int n = first + lane; n < end; n += 64) {
+            const int a0 = arc_begin[n], a1 = arc_begin[n + 1];    // (n + 1 <= n_states: the array has that entry)
+            bool wrong = a0 < 0 || a1 > n_arcs || a1 < a0 || a1 - a0 > PPG_VITERBI_MAX_DEGREE ||
+                         bad_symbol(phonemes[n]) || bad_weight(stay[n]) || bad_weight(initial[n]) ||
+                         bad_weight(final_[n]);
+            if (!wrong)
+                for (int j = a0; j < a1; ++j) wrong |= (unsigned)sources[j] >= (unsigned)S || bad_weight(weights[j]);
+            bad |= wrong;
+        }
+        fine = !__any(bad);
+        // (non-decreasing inside the graph and inside [0, n_arcs] by now)
+        if (fine) fine = arc_begin[end] - arc_begin[first] <= PPG_VITERBI_MAX_ARCS;
+    }
+    if (lane == 0) verdict[g] = fine ? 1 : 0;
+}
+
+// The arcs of one graph as the programme and the trace-back read them: Held from LDS, where a piece is (source, the
+// weight's bits), else from the caller's arrays.  `i` counts from the graph's first arc.
+template <bool Held>
+struct ViterbiArcs {
+    const uint2* held; const int* sources; const float* weights; int count;
+    __device__ __forceinline__ void get(int i, int& source, float& weight) const {
+        if (Held) {
+            const uint2 piece = held[i];
+            source = (int)piece.x; weight = __uint_as_float(piece.y);
+        } else {
+            source = sources[i]; weight = weights[i];
+        }
+    }
+};
+
+// What the programme keeps of a state in LDS: `meta`, the first arc (counted from the graph's first, 16 bits), the
+// degree (8 bits) and the phoneme (above bit 24) in one word, and the weight of staying.
+struct ViterbiTable {
+    int meta[VSTATES];
+    float stay[VSTATES];
+};
+__device__ __forceinline__ int first_arc(int meta) { return meta & 0xffff; }
+__device__ __forceinline__ int degree_of(int meta) { return (meta >> 16) & 0xff; }
+
+// Frame t of G neighbouring states n0 .. n0 + G - 1 of one lane: their D from `before` (frame t-1) into `now`, their
+// back-pointers into `row`, the frame's G bytes at n0.  `e` is the prepared frame.  G = 4 moves every per-state word
+// as one 16-byte piece.  A lane may diverge inside; call it from wave-uniform control flow.
+template <int G, bool Held>
+__device__ __forceinline__ void viterbi_states(int t, int n0, int S, const float* __restrict__ e,
+                                               const ViterbiTable& table, const float* __restrict__ initial,
+                                               const ViterbiArcs<Held>& arcs, const float* __restrict__ before,
+                                               float* __restrict__ now, uint8_t* __restrict__ row)
+{
+    static_assert(G == 1 || G == 4, "a byte or a dword of back-pointers");
+    int meta[G], from[G];
+    float own[G], d[G], best[G];
+    if constexpr (G == 4) {
+        const int4 m = *reinterpret_cast<const int4*>(table.meta + n0);
+        const float4 o = *reinterpret_cast<const float4*>(table.stay + n0);
+        const float4 b = *reinterpret_cast<const float4*>(before + n0);
+        meta[0] = m.x; meta[1] = m.y; meta[2] = m.z; meta[3] = m.w;
+        own[0] = o.x; own[1] = o.y; own[2] = o.z; own[3] = o.w;
+        d[0] = b.x; d[1] = b.y; d[2] = b.z; d[3] = b.w;
+    } else {
+        meta[0] = table.meta[n0]; own[0] = table.stay[n0]; d[0] = before[n0];
+    }
+    float cur[G];
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+        cur[k] = e[meta[k] >> 24];
+        from[k] = 0;
+    }
+    if (t == 0) {                                              // (uniform)
+#pragma unroll
+        for (int k = 0; k < G; ++k) d[k] = cur[k] + (n0 + k < S ? initial[n0 + k] : -INFINITY);
+    } else {
+#pragma unroll
+        for (int k = 0; k < G; ++k) best[k] = d[k] + own[k];   // staying: what an arc has to beat
+        if (arcs.count > 0) {                                  // (uniform) arc 0 stands in where a state has none
+#pragma unroll
+            for (int j = 0; j < VLEAD; ++j) {                  // the first arcs of the G states in lock step
+                int p[G]; float w[G];
+#pragma unroll
+                for (int k = 0; k < G; ++k) {
+                    const bool there = j < degree_of(meta[k]);
+                    arcs.get(there ? first_arc(meta[k]) + j : 0, p[k], w[k]);
+                    w[k] = there ? w[k] : -INFINITY;           // no such arc: -inf is never better
+                }
+#pragma unroll
+                for (int k = 0; k < G; ++k) {
+                    const float c = before[p[k]] + w[k];       // -inf + finite = -inf: never NaN
+                    const bool better = c > best[k];
+                    best[k] = better ? c : best[k];
+                    from[k] = better ? j + 1 : from[k];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < G; ++k) {                      // what lies beyond: state by state, in list order
+                const int at = first_arc(meta[k]), degree = degree_of(meta[k]);
+                auto batch = [&]<int N>(int j0) {              // arcs j0 .. j0 + N - 1, the loads ahead of the compares
+                    int p[N]; float w[N];
+#pragma unroll
+                    for (int u = 0; u < N; ++u)                // (past the last arc the last one again: never better)
+                        arcs.get(at + min(j0 + u, degree - 1), p[u], w[u]);
+#pragma unroll
+                    for (int u = 0; u < N; ++u) {
+                        const float c = before[p[u]] + w[u];
+                        const bool better = c > best[k];
+                        best[k] = better ? c : best[k];
+                        from[k] = better ? j0 + u + 1 : from[k];
+                    }
+                };
+                // four first (a state of a sausage has three or four arcs), then VAHEAD at a time
+                if (degree > VLEAD) batch.template operator()<4>(VLEAD);
+                for (int j0 = VLEAD + 4; j0 < degree; j0 += VAHEAD) batch.template operator()<VAHEAD>(j0);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < G; ++k) d[k] = cur[k] + best[k];
+    }
+    if constexpr (G == 4) {
+        *reinterpret_cast<float4*>(now + n0) = make_float4(d[0], d[1], d[2], d[3]);
+        *reinterpret_cast<uint32_t*>(row + n0) =
+            (uint32_t)from[0] | (uint32_t)from[1] << 8 | (uint32_t)from[2] << 16 | (uint32_t)from[3] << 24;
+    } else {
+        now[n0] = d[0];
+        row[n0] = (uint8_t)from[0];
+    }
+}
+
+// grid (items), 64 threads, `held` * 8 bytes of dynamic LDS.  G states per lane and pass: 1 if the call's graphs have
+// at most 64 states (a pass is 64 states), else 4 (a pass is 256 states; a graph takes ceil(S / 256) passes per frame).
+// `row` = viterbi_row(max_states) back-pointer bytes per frame.  An utterance whose length is impossible, whose `which`
+// names no graph or whose graph was refused gets total = NaN and runs = 0, one without a path total = -inf and runs =
+// 0; every other its total, its end state in `ends` and its back-pointers.
+template <int G>
+__global__ __launch_bounds__(64) void viterbi_programme(const float* __restrict__ logp, int frames,
+                                                         const int* __restrict__ lengths, int graphs,
+                                                         const int* __restrict__ which,
+                                                         const int* __restrict__ verdict,
+                                                         const int* __restrict__ state_begin,
+                                                         const int* __restrict__ phonemes,
+                                                         const float* __restrict__ stay,
+                                                         const float* __restrict__ initial,
+                                                         const float* __restrict__ final_,
+                                                         const int* __restrict__ arc_begin,
+                                                         const int* __restrict__ sources,
+                                                         const float* __restrict__ weights, int held, int row,
+                                                         uint8_t* __restrict__ back, int* __restrict__ ends,
+                                                         int* __restrict__ runs, float* __restrict__ total)
+{
+    __shared__ float4 stage[2][CHUNK_VEC];
+    __shared__ __attribute__((aligned(16))) float dist[2][VSTATES];
+    __shared__ __attribute__((aligned(16))) ViterbiTable table;
+    extern __shared__ uint2 held_arcs[];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item], g = which ? which[item] : 0;
+    bool fine = T >= 1 && T <= frames && (unsigned)g < (unsigned)graphs;
+    if (fine) fine = verdict[g] != 0;                          // (then S <= max_states <= row)
+    if (!fine) {                                               // (uniform)
+        if (lane == 0) { total[item] = NAN; runs[item] = 0; }
+        return;
+    }
+    const int first = state_begin[g], S = state_begin[g + 1] - first;
+    const int* begin = arc_begin + first;
+    const int arc0 = begin[0], count = begin[S] - arc0;
+    const int covered = (S + 64 * G - 1) / (64 * G) * (64 * G);    // whole passes: <= row <= VSTATES
+    for (int n = lane; n < covered; n += 64) {
+        const bool state = n < S;
+        // states at or above S run along on phoneme 0 without arcs, at -inf, unread
+        table.meta[n] = state ? (begin[n] - arc0) | (begin[n + 1] - begin[n]) << 16 | phonemes[first + n] << 24 : 0;
+        table.stay[n] = state ? stay[first + n] : -INFINITY;
+        dist[1][n] = -INFINITY;                                // what frame 0 reads as D of the frame before: unused
+    }
+    const bool keep = count <= held;                           // (uniform)
+    if (keep)
+        for (int i = lane; i < count; i += 64)
+            held_arcs[i] = make_uint2((uint32_t)sources[arc0 + i], __float_as_uint(weights[arc0 + i]));
+    const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
+    uint8_t* out = back + (size_t)item * frames * row;
+    const ViterbiArcs<true> in_lds{held_arcs, nullptr, nullptr, count};
+    const ViterbiArcs<false> in_memory{nullptr, sources + arc0, weights + arc0, count};
+    // the frame walk of WALK_FRAMES: the prepared frames through LDS CHUNK at a time, the next chunk in flight
+    float4 next[FETCH];
+    fetch(src, 0, T, lane, next);
+    stash(stage[0], lane, next);
+    __syncthreads();
+    int buf = 0;
+    for (int t0 = 0; t0 < T; t0 += CHUNK, buf ^= 1) {
+        fetch(src, t0 + CHUNK, T, lane, next);
+        const float* e = reinterpret_cast<const float*>(stage[buf]);
+        const int chunk = min(CHUNK, T - t0);
+        for (int u = 0; u < chunk; ++u) {
+            const int t = t0 + u;
+            for (int n0 = lane * G; n0 < covered; n0 += 64 * G) {  // (uniform: every lane takes every pass)
+                if (keep) viterbi_states<G, true>(t, n0, S, e + u * PREP, table, initial + first, in_lds,
+                                                  dist[(t & 1) ^ 1], dist[t & 1], out + (size_t)t * row);
+                else viterbi_states<G, false>(t, n0, S, e + u * PREP, table, initial + first, in_memory,
+                                              dist[(t & 1) ^ 1], dist[t & 1], out + (size_t)t * row);
+            }
+            __syncthreads();                                   // frame t+1 reads what this frame wrote
+        }
+        stash(stage[buf ^ 1], lane, next);                     // its readers passed the barrier above
+        __syncthreads();
+    }
+    // the first of the largest F: ascending n inside a lane, then the lower state of equal values across lanes
+    const float* last = dist[(T - 1) & 1];
+    float most = -INFINITY;
+    int end = VSTATES;
+    for (int n = lane; n < S; n += 64) {
+        const float f = last[n] + final_[first + n];
+        if (f > most || end == VSTATES) { most = f; end = n; }
+    }
+#pragma unroll
+    for (int step = 1; step < 64; step <<= 1) {
+        const float other = __shfl_xor(most, step);
+        const int state = __shfl_xor(end, step);
+        const bool better = other > most || (other == most && state < end);
+        most = better ? other : most;
+        end = better ? state : end;
+    }
+    if (lane == 0) {
+        total[item] = most;
+        if (most > -INFINITY) ends[item] = end;
+        else runs[item] = 0;                                   // no path: nothing else is written
+    }
+}
+
+// grid (items), 64 threads, `held` * 4 bytes of dynamic LDS; `row` = viterbi_row(max_states) back-pointer bytes per frame
+__global__ __launch_bounds__(64) void viterbi_traceback(const uint8_t* __restrict__ back, int frames,
+                                                         const int* __restrict__ lengths,
+                                                         const int* __restrict__ which,
+                                                         const int* __restrict__ state_begin,
+                                                         const int* __restrict__ arc_begin,
+                                                         const int* __restrict__ sources, int held, int row,
+                                                         const float* __restrict__ total,
+                                                         const int* __restrict__ ends, int* __restrict__ labels)
+{
+    __shared__ uint4 rows[VROWS_VEC];
+    extern __shared__ int held_sources[];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item];
+    if (!recognized(T, frames, total + item)) return;          // (uniform) so `which` and the graph are fine
+    const int g = which ? which[item] : 0;
+    const int first = state_begin[g], S = state_begin[g + 1] - first;
+    const int* begin = arc_begin + first;
+    const int arc0 = begin[0], count = begin[S] - arc0;
+    const bool keep = count <= held;                           // (uniform)
+    if (keep)
+        for (int i = lane; i < count; i += 64) held_sources[i] = sources[arc0 + i];   // (the loop's barriers follow)
+    // what the programme wrote of a row: the graph's own passes, not the call's largest graph's.  Only that is read.
+    const int covered = row == 64 ? 64 : (S + 255) & ~255;     // <= row
+    const int per = covered / 16;                              // 16-byte pieces per frame: 4, 16, 32, 48 or 64
+    const int span = VROWS_VEC / per;                          // frames per refill: 256, 64, 32, 21 or 16
+    const uint4* src = reinterpret_cast<const uint4*>(back + (size_t)item * frames * row);
+    int* out = labels + (size_t)item * frames;
+    constexpr int PER = VROWS_VEC / 64;
+    uint4 next[PER];
+    auto load = [&](int c) {                                   // rows of frames c * span ..., those below T only
+        const int pieces = min(span, T - c * span) * per;
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int idx = u * 64 + lane, frame = idx / per;  // (the refill stands frame by frame, `covered` bytes each)
+            next[u] = idx < pieces ? src[(size_t)(c * span + frame) * (row / 16) + idx - frame * per]
+                                   : make_uint4(0, 0, 0, 0);
+        }
+    };
+    int n = min(max(ends[item], 0), S - 1);
+    int parity = 0;
+    int c = (T - 1) / span;
+    load(c);
+    for (; c >= 0; --c) {
+        __syncthreads();                                       // the walk over the previous refill is over
+#pragma unroll
+        for (int u = 0; u < PER; ++u) rows[u * 64 + lane] = next[u];
+        __syncthreads();
+        if (c > 0) load(c - 1);
+        const uint8_t* bytes = reinterpret_cast<const uint8_t*>(rows);
+        for (int t = min(T - 1, c * span + span - 1); t >= c * span; --t) {
+            if (lane == 0) out[t] = n | parity;                // frame t's label
+            // frame t's ordinal: the same address in every lane (frame 0 has no predecessor; its byte is 0)
+            const int from = t > 0 ? bytes[(t - c * span) * covered + n] : 0;
+            if (from) {                                        // (uniform) a run opens here: through in-arc from - 1
+                const int arc = begin[n] - arc0 + from - 1;
+                n = min(max(keep ? held_sources[arc] : sources[arc0 + arc], 0), S - 1);
+                parity ^= VPARITY;
+            }
+        }
+    }
+}
+
+// grid (items), 64 threads: lane = frame of the current 64
+__global__ __launch_bounds__(64) void viterbi_runs(const int* __restrict__ labels, int frames,
+                                                    const int* __restrict__ lengths, const int* __restrict__ which,
+                                                    const int* __restrict__ state_begin,
+                                                    const int* __restrict__ state_phonemes,
+                                                    const float* __restrict__ total, int* __restrict__ states,
+                                                    int* __restrict__ phonemes, int* __restrict__ starts,
+                                                    int* __restrict__ runs)
+{
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item];
+    if (!recognized(T, frames, total + item)) return;          // (uniform) the programme has set runs = 0
+    const int* sym = state_phonemes + state_begin[which ? which[item] : 0];
+    const int* src = labels + (size_t)item * frames;
+    int* out_states = states + (size_t)item * frames;
+    int* out_phonemes = phonemes + (size_t)item * frames;
+    int* out_starts = starts + (size_t)item * (frames + 1);
+    int carry = -1, base = 0;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        open_runs(t < T ? src[t] : -2, t, T, lane, carry, base, out_states, out_starts);
+    }
+    if (lane == 0) { runs[item] = base; out_starts[base] = T; }
+    __syncthreads();                                           // the labels of the runs are written
+    for (int r = lane; r < base; r += 64) {                    // a run's label without its parity bit is its state
+        const int state = out_states[r] & (VPARITY - 1);
+        out_states[r] = state;
+        out_phonemes[r] = sym[state];
+    }
+}
+
 // ---- the rungs the host entries share, in the order every entry takes them.  Each returns PPG_OK or has left its
 // message; nothing is launched before the last of an entry's checks has passed. ----
 
@@ -1728,6 +2136,68 @@ int ppg_recognize(int device, const float* ppg, int frames, int items, const int
     hipLaunchKernelGGL(align_score, dim3((frames + 63) / 64, items), dim3(64), 0, s, logp, frames, lengths, phonemes,
                        frames, runs, total, starts, score, gop);
     return launched("recognize");
+}
+
+size_t ppg_viterbi_workspace_bytes(int items, int frames, int max_states) {
+    if (items <= 0 || items > PPG_VITERBI_MAX_ITEMS || frames <= 0 || frames > PPG_VITERBI_MAX_FRAMES ||
+        max_states <= 0 || max_states > PPG_VITERBI_MAX_STATES)
+        return 0;
+    return viterbi_layout(items, frames, max_states).bytes;
+}
+
+int ppg_viterbi(int device, const float* ppg, int frames, int items, const int32_t* lengths, int graphs, int n_states,
+                int n_arcs, int max_states, const int32_t* state_begin, const int32_t* state_phonemes,
+                const float* stay, const float* initial, const float* final_, const int32_t* arc_begin,
+                const int32_t* sources, const float* weights, const int32_t* which, int32_t* states,
+                int32_t* phonemes, int32_t* starts, int32_t* runs, float* total, float* score, float* gop,
+                void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = check_common("viterbi", ppg, frames, items, lengths, PPG_VITERBI_MAX_FRAMES,
+                                    PPG_VITERBI_MAX_ITEMS))
+        return rc;
+    if (!workspace || graphs <= 0 || n_states <= 0 || n_arcs < 0 || max_states <= 0)
+        return ppg::fail_message(PPG_EINVAL, "viterbi: bad argument");
+    if (graphs > PPG_VITERBI_MAX_GRAPHS)
+        return ppg::fail_message(PPG_EINVAL, "viterbi: %d graphs, at most %d per call", graphs, PPG_VITERBI_MAX_GRAPHS);
+    if (max_states > PPG_VITERBI_MAX_STATES)
+        return ppg::fail_message(PPG_EINVAL, "viterbi: %d states, at most %d per graph", max_states,
+                                 PPG_VITERBI_MAX_STATES);
+    if (n_states < graphs || (long long)n_states > (long long)graphs * max_states ||
+        (long long)n_arcs > (long long)graphs * PPG_VITERBI_MAX_ARCS)
+        return ppg::fail_message(PPG_EINVAL, "viterbi: %d states and %d arcs cannot be %d graphs of 1 to %d states and "
+                                 "at most %d arcs", n_states, n_arcs, graphs, max_states, PPG_VITERBI_MAX_ARCS);
+    if (n_arcs > 0 && (!sources || !weights)) return ppg::fail_message(PPG_EINVAL, "viterbi: bad argument");
+    if (const int rc = check_words("viterbi", {state_begin, state_phonemes, stay, initial, final_, arc_begin, states,
+                                               phonemes, starts, runs, total, score},
+                                   {sources, weights, which, gop, ppg, lengths}))
+        return rc;
+    const ViterbiLayout w = viterbi_layout(items, frames, max_states);
+    if (const int rc = check_workspace("viterbi", workspace, workspace_bytes, w.bytes)) return rc;
+    if (const int rc = select_device(device)) return rc;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    float* logp = reinterpret_cast<float*>(ws + w.logp);
+    uint8_t* back = reinterpret_cast<uint8_t*>(ws + w.back);
+    int* labels = reinterpret_cast<int*>(ws + w.labels);
+    int* ends = reinterpret_cast<int*>(ws + w.ends);
+    int* verdict = reinterpret_cast<int*>(ws + w.verdict);
+    // the arcs a wave keeps in LDS: no graph of the call has more than all of them
+    const int held = n_arcs < VHELD ? n_arcs : VHELD;
+    hipLaunchKernelGGL(viterbi_check, dim3(graphs), dim3(64), 0, s, n_states, n_arcs, max_states, state_begin,
+                       state_phonemes, stay, initial, final_, arc_begin, sources, weights, verdict);
+    hipLaunchKernelGGL(align_prepare, dim3((frames + 63) / 64, items), dim3(64), 0, s, ppg, frames, lengths, logp);
+    const int row = viterbi_row(max_states);
+    hipLaunchKernelGGL(row == 64 ? viterbi_programme<1> : viterbi_programme<4>, dim3(items), dim3(64),
+                       (size_t)held * sizeof(uint2), s, logp, frames, lengths, graphs, which, verdict, state_begin,
+                       state_phonemes, stay, initial, final_, arc_begin, sources, weights, held, row, back, ends, runs,
+                       total);
+    hipLaunchKernelGGL(viterbi_traceback, dim3(items), dim3(64), (size_t)held * sizeof(int), s, back, frames, lengths,
+                       which, state_begin, arc_begin, sources, held, row, total, ends, labels);
+    hipLaunchKernelGGL(viterbi_runs, dim3(items), dim3(64), 0, s, labels, frames, lengths, which, state_begin,
+                       state_phonemes, total, states, phonemes, starts, runs);
+    // the runs as a transcript: at most `frames` phonemes, `runs` of them
+    hipLaunchKernelGGL(align_score, dim3((frames + 63) / 64, items), dim3(64), 0, s, logp, frames, lengths, phonemes,
+                       frames, runs, total, starts, score, gop);
+    return launched("viterbi");
 }
 
 size_t ppg_search_workspace_bytes(int items, int frames, int queries) {

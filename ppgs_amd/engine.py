@@ -167,6 +167,13 @@ SYMBOLS = {
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'ppg_viterbi_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_viterbi': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'ppg_search_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'ppg_search': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
@@ -882,6 +889,84 @@ def recognize_items(ppg, lengths, transitions, initial=None, final=None, want_go
                 runs[at:].data_ptr(), total[at:].data_ptr(), score[at:].data_ptr(),
                 gop[at:].data_ptr() if want_gop else None, workspace.data_ptr(), size, stream))
     return phonemes, starts, runs, total, score, gop
+
+
+VITERBI_MAX_STATES = 1024        # PPG_VITERBI_MAX_STATES, per graph
+VITERBI_MAX_ARCS = 32768         # PPG_VITERBI_MAX_ARCS, per graph
+VITERBI_MAX_DEGREE = 255         # PPG_VITERBI_MAX_DEGREE: in-arcs of one state
+VITERBI_MAX_FRAMES = 262144      # PPG_VITERBI_MAX_FRAMES
+VITERBI_MAX_ITEMS = 65535        # PPG_VITERBI_MAX_ITEMS, per call of the library
+VITERBI_MAX_GRAPHS = 65535       # PPG_VITERBI_MAX_GRAPHS, per call of the library
+VITERBI_WORKSPACE_BYTES = 1 << 30  # a larger batch runs as several calls, each within this much workspace
+
+
+def viterbi_items(ppg, lengths, state_begin, phonemes, stay, initial, final, arc_begin, sources, weights, which=None,
+                  max_states=None, want_gop=True):
+    """The best path of item b = ppg[b, :, :lengths[b]] through graph which[b] (ppg_viterbi).  The graphs travel
+    packed, as the library takes them: state_begin (graphs + 1,), phonemes, stay, initial and final over all states,
+    arc_begin (states + 1,), sources (counted inside each graph) and weights over all arcs; integer tensors become
+    int32 and the weights fp32 on the device of `ppg`.  `which` holds a graph per item as host integers (None: graph 0
+    for all); max_states bounds every graph's states (None: the library's limit or the number of states, whichever is
+    less).  Nothing of the graphs is checked here: the device checks them, and an item whose graph it refuses, whose
+    `which` names no graph or whose length is impossible has total NaN and runs 0.  (items, 40, frames) on a GPU ->
+    states and phonemes (items, frames) int32, starts (items, frames + 1) int32, runs (items,) int32, total (items,)
+    fp32, score and gop (items, frames) fp32 (gop None without want_gop).  Entries past an item's runs (runs + 1 for
+    starts) are zero; an item without a path has runs = 0 and total = -inf."""
+    x, lengths = _items(ppg, lengths, 'viterbi', VITERBI_MAX_FRAMES)
+    items, frames = x.shape[0], x.shape[2]
+    device = x.device
+
+    def words(tensor, dtype, name):
+        tensor = torch.as_tensor(tensor)
+        if tensor.dim() != 1:
+            raise ValueError(f'{name} must be one-dimensional, got {tuple(tensor.shape)}')
+        return tensor.to(device=device, dtype=dtype).contiguous()
+    state_begin, arc_begin = words(state_begin, torch.int32, 'state_begin'), words(arc_begin, torch.int32, 'arc_begin')
+    phonemes, sources = words(phonemes, torch.int32, 'phonemes'), words(sources, torch.int32, 'sources')
+    stay, initial = words(stay, torch.float32, 'stay'), words(initial, torch.float32, 'initial')
+    final, weights = words(final, torch.float32, 'final'), words(weights, torch.float32, 'weights')
+    graphs, count, arcs = state_begin.shape[0] - 1, phonemes.shape[0], sources.shape[0]
+    if graphs < 1 or count < 1:
+        raise ValueError('viterbi takes at least one graph of at least one state')
+    for name, tensor, size in (('stay', stay, count), ('initial', initial, count), ('final', final, count),
+                               ('arc_begin', arc_begin, count + 1), ('weights', weights, arcs)):
+        if tensor.shape[0] != size:
+            raise ValueError(f'{name} has {tensor.shape[0]} entries, {size} expected')
+    if max_states is None:
+        max_states = min(VITERBI_MAX_STATES, count)
+    if which is not None:
+        which = [int(v) for v in which]
+        if len(which) != items:
+            raise ValueError(f'{len(which)} graphs named for {items} items')
+        which = torch.tensor(which, dtype=torch.int32).to(device)
+    lengths = torch.tensor(lengths, dtype=torch.int32).to(device)
+    states = torch.zeros((items, frames), dtype=torch.int32, device=device)
+    labels = torch.zeros((items, frames), dtype=torch.int32, device=device)
+    starts = torch.zeros((items, frames + 1), dtype=torch.int32, device=device)
+    runs = torch.empty((items,), dtype=torch.int32, device=device)
+    total = torch.empty((items,), dtype=torch.float32, device=device)
+    score = torch.zeros((items, frames), dtype=torch.float32, device=device)
+    gop = torch.zeros((items, frames), dtype=torch.float32, device=device) if want_gop else None
+    lib = library()
+    bytes_for = lib.ppg_viterbi_workspace_bytes
+    one = bytes_for(1, frames, max_states)
+    if one == 0:
+        raise ValueError(f'viterbi takes graphs of 1 to {VITERBI_MAX_STATES} states, got max_states = {max_states}')
+    group = max(1, min(items, VITERBI_MAX_ITEMS, VITERBI_WORKSPACE_BYTES // one))
+    size = bytes_for(group, frames, max_states)
+    workspace = torch.empty((size,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for at in range(0, items, group):
+            _check(lib.ppg_viterbi(
+                device.index, x[at:].data_ptr(), frames, min(group, items - at), lengths[at:].data_ptr(), graphs, count,
+                arcs, max_states, state_begin.data_ptr(), phonemes.data_ptr(), stay.data_ptr(), initial.data_ptr(),
+                final.data_ptr(), arc_begin.data_ptr(), sources.data_ptr() if arcs else None,
+                weights.data_ptr() if arcs else None, None if which is None else which[at:].data_ptr(),
+                states[at:].data_ptr(), labels[at:].data_ptr(), starts[at:].data_ptr(), runs[at:].data_ptr(),
+                total[at:].data_ptr(), score[at:].data_ptr(), gop[at:].data_ptr() if want_gop else None,
+                workspace.data_ptr(), size, stream))
+    return states, labels, starts, runs, total, score, gop
 
 
 SEARCH_MAX_FRAMES = 262144       # PPG_SEARCH_MAX_FRAMES
