@@ -913,6 +913,83 @@ int ppg_recognize_stream_flush(int device, void* state, int streams, int window,
                                float* score, float* gop, int32_t* count, float* total, int32_t* forced, void* stream);
 
 /*
+ * Live Viterbi over a phoneme graph: ppg_viterbi carried across the pushes of a stream, as ppg_recognize_stream_* carries
+ * ppg_recognize.  The stream rules are those above with a state n of the stream's graph wherever they have a phoneme q,
+ * and the graph, its limits, weights and recurrence are ppg_viterbi's.  Not in the reference.
+ *
+ * One stream has a position p, a commit point c, D[0 .. S) of frame p-1, a ring of `window` = W frames with the
+ * back-pointer rows (one byte per state, the ordinal `from` of ppg_viterbi), the prepared frames and the labels of the
+ * frames in [c, p), one open run, the counter `forced`, the graph it was opened with, and every state's ancestor
+ * path(n, c), carried forward frame by frame.
+ *   Forward.  ppg_viterbi's recurrence, unchanged, D[0, n] = e[0, n] + initial[n] at absolute frame 0: for any split into
+ *   pushes, D and the back-pointer byte of every frame and state are the bits ppg_viterbi computes for the whole recording.
+ *   Commit, once per stream and push: the natural and the forced commit of ppg_recognize_stream_push, over the states.
+ *   Runs.  A committed frame opens a run if it is absolute frame 0 or its back-pointer byte at its state is not 0 (two
+ *   runs of one state follow each other through an arc n -> n); else it extends the open run.  A closed run is emitted as
+ *   (state, phoneme, begin, end, sum / float(end - begin), below / float(end - begin)).
+ *   flush: F[n] = D[n] + final[n]; last = the first n with the largest F; total = F[last]; if total > -inf everything up to
+ *   p is committed along path(last, .); the open run is closed, total and forced are reported and the stream starts again
+ *   at frame 0 with the same graph.
+ *   If forced == 0 and ppg_viterbi finds a path, the runs of all pushes and of the flush, concatenated, are ppg_viterbi's
+ *   states, phonemes, starts, score and gop of the whole recording and flush's total is its total, bit for bit, for every
+ *   split.  Under the graph of a transition model every output equals ppg_recognize_stream_*'s, forced commits included.
+ *   With a left-to-right chain nothing commits naturally; max_lag = L makes the stream a forced alignment with a latency
+ *   of L frames.
+ *
+ * The caller owns the state (device memory, 16-byte aligned, ppg_viterbi_stream_state_bytes(streams, window, max_states)
+ * bytes); there is no handle.  With row = 64 if max_states <= 64, else max_states rounded up to 256: seven blocks, each
+ * 256-byte aligned: the head of every stream (8 words: p, c, forced, the open run's state or -1, its start, sum, below,
+ * the stream's graph or -1), D (row fp32 per stream), the ancestors (row 16-bit words per stream), the back-pointer rings
+ * (window * row bytes per stream), the rings of prepared frames (176 B per frame), the rings of labels (int32), and the
+ * verdicts on the graphs (int32, room for `streams`).
+ *
+ * ppg_viterbi_stream_open: the graph arguments are ppg_viterbi's packed arrays, graphs <= streams; which_graph is device
+ * int32[streams], the graph of every stream, or NULL for graph 0.  It checks every graph on the device as ppg_viterbi
+ * does, once, leaves the verdicts in the state, records every stream's graph and resets every stream.  A stream whose
+ * graph was refused or whose index names no graph answers count = -1 to every push and count = 0, total = NaN, forced =
+ * -1 to every flush until the state is opened again.
+ * ppg_viterbi_stream_push and _flush take the graph arrays again and go by the stored verdicts: they MUST be the arrays,
+ * with the same contents, the state was opened with.  (A source read from them is clamped into [0, S) wherever the live
+ * kernels index with it themselves.)  Otherwise as ppg_recognize_stream_push and _flush, with `states` (streams, cap)
+ * beside `phonemes`; final_ is not read by a push.  A stream with (p - c) + lengths[i] > W, a length outside [0, frames]
+ * or a position that would pass INT32_MAX gets count = -1 and keeps its state.  ppg_viterbi_stream_reset and _flush take
+ * `which`, device int32[streams] flags of the streams meant, or NULL for all.
+ * Kernel launches on `stream` only: no allocation, synchronisation or copy.  Every byte a kernel reads was written by
+ * open, reset or an earlier kernel of the same sequence of calls.  Every stream's results are a function of that stream
+ * alone.
+ * PPG_EINVAL, and nothing launched, for: more than PPG_VITERBI_STREAM_MAX_STREAMS streams, a window that is not a
+ * multiple of 64 in [PPG_VITERBI_STREAM_MIN_WINDOW, PPG_VITERBI_STREAM_MAX_WINDOW], max_states outside
+ * 1 .. PPG_VITERBI_MAX_STATES, graphs outside 1 .. streams, n_states or n_arcs that cannot be (as for ppg_viterbi), frames
+ * outside 1 .. PPG_VITERBI_MAX_FRAMES, max_lag outside [0, window), cap < 1, a NULL or unaligned (16 bytes for the state
+ * and the workspace, 4 for the others) state, workspace, input or output, a short workspace.  The two *_bytes helpers are
+ * host-only and return 0 for impossible arguments.
+ */
+#define PPG_VITERBI_STREAM_MIN_WINDOW 64
+#define PPG_VITERBI_STREAM_MAX_WINDOW 65536
+#define PPG_VITERBI_STREAM_MAX_STREAMS 65535
+size_t ppg_viterbi_stream_state_bytes(int streams, int window, int max_states);
+size_t ppg_viterbi_stream_workspace_bytes(int streams, int frames);
+int ppg_viterbi_stream_open(int device, void* state, int streams, int window, int graphs, int n_states, int n_arcs,
+                            int max_states, const int32_t* state_begin, const int32_t* state_phonemes,
+                            const float* stay, const float* initial, const float* final_, const int32_t* arc_begin,
+                            const int32_t* sources, const float* weights, const int32_t* which_graph, void* stream);
+int ppg_viterbi_stream_reset(int device, void* state, int streams, int window, int max_states, const int32_t* which,
+                             void* stream);
+int ppg_viterbi_stream_push(int device, void* state, int streams, int window, const float* ppg, int frames,
+                            const int32_t* lengths, int graphs, int n_states, int n_arcs, int max_states,
+                            const int32_t* state_begin, const int32_t* state_phonemes, const float* stay,
+                            const float* initial, const float* final_, const int32_t* arc_begin,
+                            const int32_t* sources, const float* weights, int max_lag, int cap, int32_t* states,
+                            int32_t* phonemes, int32_t* begin, int32_t* end, float* score, float* gop, int32_t* count,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int ppg_viterbi_stream_flush(int device, void* state, int streams, int window, int graphs, int n_states, int n_arcs,
+                             int max_states, const int32_t* state_begin, const int32_t* state_phonemes,
+                             const float* stay, const float* initial, const float* final_, const int32_t* arc_begin,
+                             const int32_t* sources, const float* weights, const int32_t* which, int cap,
+                             int32_t* states, int32_t* phonemes, int32_t* begin, int32_t* end, float* score,
+                             float* gop, int32_t* count, float* total, int32_t* forced, void* stream);
+
+/*
  * Frame metrics accumulated on the device: what the reference's `python -m ppgs.evaluate` computes per batch with
  * five metric objects (ppgs/evaluate/metrics.py: Accuracy, CategoricalAccuracy, JensenShannon, TopKAccuracy, Loss,
  * DistanceMatrix), here ONE kernel launch per batch into one device block, no host synchronisation, read once at

@@ -70,7 +70,8 @@ are special graphs (`chain_graph`, `model_graph`) and `viterbi` equals them bit 
     path = ppgs_amd.alignment.viterbi(ppg, graph)
     said = [variant_of[n] for n in path.states.tolist()]                       # which variant each run belongs to
     graph, word_of = ppgs_amd.alignment.word_loop({'yes': [['y', 'eh', 's']], 'no': [['n', 'ow']]}, penalty=2.)
-Not here: a streaming form, states that emit nothing, N-best lists, minimum durations, more than 1024 states.
+Not here: states that emit nothing, N-best lists, minimum durations, more than 1024 states.  The live form is
+`ViterbiStream` (ppg_viterbi_stream_*): `RecognizeStream`'s rules with a state of the graph in the place of a phoneme.
 
 Optional phonemes (`forced(..., optional=flags)`, ppg_align_optional): a speaker pauses between words wherever they
 like, and drops a final consonant or a schwa.  flags[n] lets the path leave phoneme n out:
@@ -181,6 +182,7 @@ Graph = collections.namedtuple('Graph', ['phonemes', 'stay', 'offsets', 'sources
 Path = collections.namedtuple('Path', ['states', 'phonemes', 'starts', 'total', 'score', 'gop'])
 Hits = collections.namedtuple('Hits', ['phonemes', 'begin', 'end', 'total', 'mean', 'count', 'curve'])
 Runs = collections.namedtuple('Runs', ['phonemes', 'begin', 'end', 'score', 'gop', 'count', 'total', 'forced'])
+StateRuns = collections.namedtuple('StateRuns', ('states',) + Runs._fields)
 
 
 def _ppg(ppg, most=MAX_FRAMES, what='alignment'):
@@ -841,6 +843,36 @@ def _checked_graph(value):
     return value
 
 
+def _graph_list(graph, batch, where, members):
+    """The distinct graphs of a call, checked, and the graph of every member (None: the one graph for all): `graph` is
+    one Graph, or with `batch` members a list of as many, in which one object may stand for several and travels once."""
+    if isinstance(graph, (list, tuple)) and not isinstance(graph, Graph):
+        if batch is None or len(graph) != batch:
+            raise ValueError(f'a list of graphs goes with {where} of as many {members}, got {len(graph)} for {batch}')
+        packed, places, which = [], {}, []
+        for value in graph:
+            if id(value) not in places:
+                places[id(value)] = len(packed)
+                packed.append(_checked_graph(value))
+            which.append(places[id(value)])
+        return packed, which
+    return [_checked_graph(graph)], None
+
+
+def _joined_graphs(packed):
+    """Checked graphs as the library takes them packed: (states per graph, state_begin, arc_begin, joined), where
+    joined(name) is that field of all graphs behind one another."""
+    counts = [value.phonemes.shape[0] for value in packed]
+    state_begin = torch.tensor([0] + counts, dtype=torch.int64).cumsum(0)
+    arc_base = torch.tensor([0] + [value.sources.shape[0] for value in packed], dtype=torch.int64).cumsum(0)
+    arc_begin = torch.cat([value.offsets[:-1].to(torch.int64) + arc_base[g] for g, value in enumerate(packed)] +
+                          [arc_base[-1:]])
+
+    def joined(name):
+        return torch.cat([getattr(value, name) for value in packed])
+    return counts, state_begin, arc_begin, joined
+
+
 def viterbi(ppg, graph, lengths=None, gop=True):
     """The best path of `ppg` through a graph of phoneme states (see the module's text): Path(states, phonemes,
     starts, total, score, gop), one entry per run of the path.
@@ -858,26 +890,8 @@ def viterbi(ppg, graph, lengths=None, gop=True):
     if not batched and lengths is not None:
         raise ValueError('lengths go with a batch: slice a single PPG instead')
     lengths = _lengths(lengths, batch, frames)
-    which = None
-    if isinstance(graph, (list, tuple)) and not isinstance(graph, Graph):
-        if not batched or len(graph) != batch:
-            raise ValueError(f'a list of graphs goes with a batch of as many items, got {len(graph)} for {batch}')
-        packed, places, which = [], {}, []
-        for value in graph:
-            if id(value) not in places:
-                places[id(value)] = len(packed)
-                packed.append(_checked_graph(value))
-            which.append(places[id(value)])
-    else:
-        packed = [_checked_graph(graph)]
-    counts = [value.phonemes.shape[0] for value in packed]
-    state_begin = torch.tensor([0] + counts, dtype=torch.int64).cumsum(0)
-    arc_base = torch.tensor([0] + [value.sources.shape[0] for value in packed], dtype=torch.int64).cumsum(0)
-    arc_begin = torch.cat([value.offsets[:-1].to(torch.int64) + arc_base[g] for g, value in enumerate(packed)] +
-                          [arc_base[-1:]])
-
-    def joined(name):
-        return torch.cat([getattr(value, name) for value in packed])
+    packed, which = _graph_list(graph, batch if batched else None, 'a batch', 'items')
+    counts, state_begin, arc_begin, joined = _joined_graphs(packed)
     device = core.device_for(None, ppg)
     x = ppg.to(device)
     states, phonemes, starts, runs, total, score, below = engine.viterbi_items(
@@ -1146,6 +1160,10 @@ class RecognizeStream:
         self._host = (_weights(transitions, (count, count), 'transitions').cpu().contiguous(),
                       None if initial is None else _weights(initial, (count,), 'initial').cpu().contiguous(),
                       None if final is None else _weights(final, (count,), 'final').cpu().contiguous())
+        self._geometry(max_lag, window, batch, gop, device)
+
+    def _geometry(self, max_lag, window, batch, gop, device):
+        """The ring, the lag and the streams, checked; nothing of the device yet."""
         if (isinstance(window, bool) or not isinstance(window, int) or window % 64 or
                 not engine.RECOGNIZE_STREAM_MIN_WINDOW <= window <= engine.RECOGNIZE_STREAM_MAX_WINDOW):
             raise ValueError(f'window must be a multiple of 64 from {engine.RECOGNIZE_STREAM_MIN_WINDOW} to '
@@ -1171,15 +1189,38 @@ class RecognizeStream:
         """The device side, made at the first call that needs it."""
         if self._state is None:
             device = core.device_for(self._gpu, tensor)
-            self._weights = tuple(None if value is None else value.to(device) for value in self._host)
             with torch.cuda.device(device):
-                self._state = engine.recognize_stream_state(device, self._streams, self.window)
+                self._state = self._open(device)
         return self._state.device
 
-    def _runs(self, phonemes, begin, end, score, gop, count, total=None, forced=None):
+    # the device calls: what ViterbiStream replaces
+    def _open(self, device):
+        self._weights = tuple(None if value is None else value.to(device) for value in self._host)
+        return engine.recognize_stream_state(device, self._streams, self.window)
+
+    def _push_piece(self, x, lengths, cap):
+        return engine.recognize_stream_push(self._state, self.window, x, lengths, self._weights[0], self._weights[1],
+                                            self.max_lag, cap, self._workspace, self.gop)
+
+    def _flush_all(self, which):
+        return engine.recognize_stream_flush(self._state, self._streams, self.window, self._weights[2],
+                                             self.max_lag + 1, which, self.gop)
+
+    def _reset_all(self, which):
+        engine.recognize_stream_reset(self._state, self._streams, self.window, which)
+
+    @staticmethod
+    def _workspace_bytes(streams, frames):
+        return engine.library().ppg_recognize_stream_workspace_bytes(streams, frames)
+
+    _tuple = Runs                                                        # what push and flush return
+
+    def _runs(self, *outputs):
+        """The outputs of a push (without total and forced) or of a flush as the stream's tuple."""
         def drop(tensor):
             return tensor if tensor is None or self.batch is not None else tensor[0]
-        return Runs(*[drop(tensor) for tensor in (phonemes, begin, end, score, gop, count, total, forced)])
+        outputs = outputs + (None,) * (len(self._tuple._fields) - len(outputs))
+        return self._tuple(*[drop(tensor) for tensor in outputs])
 
     def _which(self, item):
         """The flags of `item` for flush and reset: None for every stream."""
@@ -1222,8 +1263,8 @@ class RecognizeStream:
         if frames == 0:
             def empty(dtype):
                 return torch.empty((self._streams, 0), dtype=dtype, device=device)
-            return self._runs(empty(torch.int32), empty(torch.int32), empty(torch.int32), empty(torch.float32),
-                              empty(torch.float32) if self.gop else None,
+            integers = [empty(torch.int32) for _ in range(len(self._tuple._fields) - 5)]    # all but score .. forced
+            return self._runs(*integers, empty(torch.float32), empty(torch.float32) if self.gop else None,
                               torch.zeros((self._streams,), dtype=torch.int32, device=device))
         x = ppg.to(device=device, dtype=torch.float32)
         x = x if self.batch is not None else x[None]
@@ -1231,10 +1272,9 @@ class RecognizeStream:
         whole = None
         if lengths is not None:                                          # through pinned memory: the copy does not wait
             whole = torch.tensor(own, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
-        need = engine.library().ppg_recognize_stream_workspace_bytes(self._streams, min(frames, piece))
+        need = self._workspace_bytes(self._streams, min(frames, piece))
         if self._workspace is None or self._workspace.numel() < need:
             self._workspace = torch.empty((need,), dtype=torch.uint8, device=device)
-        transitions, initial, _ = self._weights
         packed = None
         for at in range(0, frames, piece):
             size = min(piece, frames - at)
@@ -1246,54 +1286,108 @@ class RecognizeStream:
                 on_device = self._uniform[size]
             else:
                 on_device = (whole - at).clamp_(0, size)
-            part = engine.recognize_stream_push(
-                self._state, self.window, x[:, :, at:at + size].contiguous(), on_device, transitions, initial,
-                self.max_lag, cap if frames <= piece else self.max_lag + size, self._workspace, self.gop)
+            part = self._push_piece(x[:, :, at:at + size].contiguous(), on_device,
+                                    cap if frames <= piece else self.max_lag + size)
             if frames <= piece:
                 packed = part
                 break
             packed = self._pack(packed, part, cap)
         if frames > piece:                                               # without the slot that took what was past count
-            packed = tuple(None if tensor is None else tensor[:, :cap] for tensor in packed[:5]) + (packed[5],)
+            packed = tuple(None if tensor is None else tensor[:, :cap] for tensor in packed[:-1]) + (packed[-1],)
         self._position = [position + value for position, value in zip(self._position, own)]
         return self._runs(*packed)
 
     def _pack(self, packed, part, cap):
         """The runs of a piece behind those of the pieces before it, on the device: the counts add up (-1 stays)."""
-        count = part[5]
+        count = part[-1]
         if packed is None:
             device = count.device
             packed = tuple(
                 None if tensor is None else torch.full(
                     (self._streams, cap + 1), math.nan if tensor.is_floating_point() else -1, dtype=tensor.dtype,
-                    device=device) for tensor in part[:5]) + (torch.zeros_like(count),)
+                    device=device) for tensor in part[:-1]) + (torch.zeros_like(count),)
         slots = torch.arange(part[0].shape[1], device=count.device)[None, :]
-        fits = (slots < count[:, None]) & (packed[5][:, None] >= 0)
-        where = torch.where(fits, (packed[5][:, None] + slots).clamp_(max=cap), cap).to(torch.int64)
-        for into, tensor in zip(packed[:5], part[:5]):
+        fits = (slots < count[:, None]) & (packed[-1][:, None] >= 0)
+        where = torch.where(fits, (packed[-1][:, None] + slots).clamp_(max=cap), cap).to(torch.int64)
+        for into, tensor in zip(packed[:-1], part[:-1]):
             if tensor is not None:
                 into.scatter_(1, where, tensor)
                 into[:, cap] = math.nan if tensor.is_floating_point() else -1
-        total = torch.where((packed[5] < 0) | (count < 0), torch.full_like(count, -1), packed[5] + count)
-        return packed[:5] + (total,)
+        total = torch.where((packed[-1] < 0) | (count < 0), torch.full_like(count, -1), packed[-1] + count)
+        return packed[:-1] + (total,)
 
     def flush(self, item=None):
         which = self._which(item)
         self._ensure()
-        out = engine.recognize_stream_flush(self._state, self._streams, self.window, self._weights[2], self.max_lag + 1,
-                                            which, self.gop)
+        out = self._flush_all(which)
         self._position = [0 if item is None or b == item else position for b, position in enumerate(self._position)]
         return self._runs(*out)
 
     def reset(self, item=None):
         which = self._which(item)
         self._ensure()
-        engine.recognize_stream_reset(self._state, self._streams, self.window, which)
+        self._reset_all(which)
         self._position = [0 if item is None or b == item else position for b, position in enumerate(self._position)]
 
 
+class ViterbiStream(RecognizeStream):
+    """`viterbi` on a live stream: the frames come a few at a time, the decode through the graph is carried across the
+    pushes on the device, and runs of states come out as soon as they are final.
+
+        heard = ppgs_amd.alignment.ViterbiStream(ppgs_amd.alignment.word_loop(lexicon)[0])
+        for piece in pieces:                                     # each (40, k), k >= 0
+            for name, start, end, score, gop in ppgs_amd.alignment.run_segments(heard.push(piece)): ...
+        last = heard.flush()
+
+    `graph` is a Graph (`graph`, `chain_graph`, `model_graph`, `pronunciations`, `word_loop`) for every stream, or with
+    `batch=B` a list of B of them (the same object may stand for several streams and travels once), validated as
+    `viterbi` validates it.  `window`, `max_lag` (None: window // 2), `batch`, `gop`, `device`, push, flush, reset and
+    `position` are RecognizeStream's, and so are the rules of the stream with a state of the graph in the place of a
+    phoneme; push and flush return `StateRuns(states, phonemes, begin, end, score, gop, count, total, forced)`, which
+    `run_segments` takes as it takes Runs.  A run is a stretch of frames in one state; a path that leaves a state through
+    an arc back into it opens a new run of that state.  As long as nothing is forced (`forced` == 0 at the flush) the
+    runs of all pushes and of the flush are `viterbi` of the whole recording bit for bit; under `model_graph` every
+    output equals RecognizeStream's.  In a left-to-right chain (`chain_graph`) the first state stays alive for ever, so
+    nothing commits naturally: there `max_lag` = L makes the stream a forced alignment with a latency of L frames, and
+    the states whose history disagrees with what was given out are cut off at each forced step."""
+
+    _tuple = StateRuns
+
+    def __init__(self, graph, max_lag=None, window=1024, batch=None, gop=True, device=None):
+        self._geometry(max_lag, window, batch, gop, device)
+        packed, which = _graph_list(graph, batch, 'batch=', 'streams')
+        counts, state_begin, arc_begin, joined = _joined_graphs(packed)
+        self._graphs = engine.PackedGraphs(
+            len(packed), sum(counts), int(arc_begin[-1]), max(counts), state_begin.to(torch.int32),
+            joined('phonemes').to(torch.int32), joined('stay').to(torch.float32), joined('initial').to(torch.float32),
+            joined('final').to(torch.float32), arc_begin.to(torch.int32), joined('sources').to(torch.int32),
+            joined('weights').to(torch.float32))
+        self._which_graph = None if which is None else torch.tensor(which, dtype=torch.int32)
+
+    def _open(self, device):
+        self._weights = engine.PackedGraphs(*[value.to(device).contiguous() if torch.is_tensor(value) else value
+                                              for value in self._graphs])
+        which = None if self._which_graph is None else self._which_graph.to(device)
+        return engine.viterbi_stream_state(device, self._streams, self.window, self._weights, which)
+
+    def _push_piece(self, x, lengths, cap):
+        return engine.viterbi_stream_push(self._state, self.window, x, lengths, self._weights, self.max_lag, cap,
+                                          self._workspace, self.gop)
+
+    def _flush_all(self, which):
+        return engine.viterbi_stream_flush(self._state, self._streams, self.window, self._weights, self.max_lag + 1,
+                                           which, self.gop)
+
+    def _reset_all(self, which):
+        engine.viterbi_stream_reset(self._state, self._streams, self.window, self._weights.max_states, which)
+
+    @staticmethod
+    def _workspace_bytes(streams, frames):
+        return engine.library().ppg_viterbi_stream_workspace_bytes(streams, frames)
+
+
 def run_segments(runs, sample_rate=config.SAMPLE_RATE, hopsize=config.HOPSIZE):
-    """The runs of a push or a flush as a host list of (phoneme name, start seconds, end seconds, score, gop), the first
+    """The runs of a push or a flush (Runs or StateRuns) as a host list of (phoneme name, start seconds, end seconds, score, gop), the first
     `count` of them, in stream order (gop None if the stream keeps none); a batch of streams gives a list of such
     lists.  Host only: this is where the results are read."""
     phonemes, begin, end = runs.phonemes.tolist(), runs.begin.tolist(), runs.end.tolist()

@@ -1659,11 +1659,18 @@ __device__ __forceinline__ int degree_of(int meta) { return (meta >> 16) & 0xff;
 // Frame t of G neighbouring states n0 .. n0 + G - 1 of one lane: their D from `before` (frame t-1) into `now`, their
 // back-pointers into `row`, the frame's G bytes at n0.  `e` is the prepared frame.  G = 4 moves every per-state word
 // as one 16-byte piece.  A lane may diverge inside; call it from wave-uniform control flow.
-template <int G, bool Held>
+// `along` is told every state's `meta` and `from` once they stand: the live programme carries its ancestors there.
+struct ViterbiAlone {
+    template <int G>
+    __device__ __forceinline__ void operator()(int, const int (&)[G], const int (&)[G]) const {}
+};
+
+template <int G, bool Held, class Along = ViterbiAlone>
 __device__ __forceinline__ void viterbi_states(int t, int n0, int S, const float* __restrict__ e,
                                                const ViterbiTable& table, const float* __restrict__ initial,
                                                const ViterbiArcs<Held>& arcs, const float* __restrict__ before,
-                                               float* __restrict__ now, uint8_t* __restrict__ row)
+                                               float* __restrict__ now, uint8_t* __restrict__ row,
+                                               const Along& along = Along())
 {
     static_assert(G == 1 || G == 4, "a byte or a dword of back-pointers");
     int meta[G], from[G];
@@ -1732,6 +1739,7 @@ __device__ __forceinline__ void viterbi_states(int t, int n0, int S, const float
 #pragma unroll
         for (int k = 0; k < G; ++k) d[k] = cur[k] + best[k];
     }
+    along(n0, meta, from);
     if constexpr (G == 4) {
         *reinterpret_cast<float4*>(now + n0) = make_float4(d[0], d[1], d[2], d[3]);
         *reinterpret_cast<uint32_t*>(row + n0) =
@@ -1934,6 +1942,651 @@ __global__ __launch_bounds__(64) void viterbi_runs(const int* __restrict__ label
     }
 }
 
+// ---- live Viterbi over a phoneme graph (ppg_viterbi_stream_*) ----
+//
+// ppg_viterbi carried across the pushes of a stream, under the stream rules of the live recogniser above with a state n
+// of the stream's graph wherever that text has a phoneme q: position p, commit point c, D of frame p-1, a ring of W
+// frames (slot t % W) with the back-pointer rows (one byte per state, the ordinal `from`), the prepared frames and the
+// labels of the frames in [c, p), one open run, the counter `forced`, and the graph the stream was opened with.
+//   Forward: viterbi_states, the body of viterbi_programme, with the absolute frame: D and the back-pointer byte of every
+//   frame and state are the bits viterbi_programme computes for the whole recording, whatever the pushes.
+//   Commit: natural and forced as above.  A committed frame opens a run if it is absolute frame 0 or its back-pointer
+//   byte at its state is not 0; a closed run is emitted as (state, phoneme, begin, end, score, gop).
+// The caller owns the state: seven blocks, each 256-byte aligned: the heads (8 words), D (viterbi_row(max_states) words
+// per stream), the ancestors (as many 16-bit words: anc[n] = path(n, c)), the back-pointer rings (W rows of
+// viterbi_row(max_states) bytes), the rings of prepared frames (176 B per frame) and of labels (int32), and one verdict
+// per graph (room for as many graphs as streams).  ppg_viterbi_stream_open runs viterbi_check once and records every
+// stream's graph, -1 for a graph that was refused or is not there; such a stream answers -1 to every push.  Push and
+// flush read the graph arrays again and trust them as the verdict allows; a source read from them is clamped into
+// [0, S) wherever these kernels index with it themselves.  One wave per stream:
+//   viterbi_stream_programme  copies the push's prepared frames into the ring, loads D and the ancestors into LDS, runs
+//                             viterbi_states per frame and pass, which hands `from` to ViterbiAncestors: anc[n] = n at
+//                             frame c, else anc[n] where from = 0, else anc[source of in-arc from - 1], in two more LDS
+//                             buffers of 1024 x 16 bits.
+//   viterbi_stream_commit     a ballot over the alive states' ancestors: if they differ and nothing has to be forced,
+//                             nothing can be committed.  Else the SET of the alive paths' states is walked back from t,
+//                             flags in LDS, every lane mapping its states of the set to their predecessors, until the
+//                             set is one state: that frame is v.  One wave-uniform walk as in viterbi_traceback, from
+//                             that state at v or from the best state at t if a commit is forced, writes the labels: the
+//                             state and one more bit where a run opens.  If c moved, a forward pass over the frames
+//                             (new c, t] gives every state's ancestor at the new c for the next push, and in the forced
+//                             case, through one more look-up at frame p-L, the states whose path left the one given
+//                             out: their D becomes -inf.  Then the run pass of the live recogniser on the new labels:
+//                             lane = frame, a ballot of the frames that open a run, the sums in frame order.
+//                             Back-pointer rows come through LDS 16 KiB at a time, the next refill in flight, and of a
+//                             row only the graph's own passes.
+//   viterbi_stream_advance, viterbi_stream_flush, viterbi_stream_reset (which also opens) as their namesakes above.
+
+struct ViterbiHead {
+    int position, commit, forced;
+    int label, start;                         // the open run: its state, -1: none
+    float sum, below;
+    int graph;                                // the stream's graph; -1: refused or missing when the stream was opened
+};
+static_assert(sizeof(ViterbiHead) == HEAD * 4, "the head is 8 words");
+
+struct ViterbiStreamLayout {
+    size_t heads, d, anc, back, kept, labels, verdict, bytes;      // byte offsets into the state
+};
+
+// (65535 streams of 65536 frames and 1024 states are 5.2e12 bytes: inside a size_t)
+inline ViterbiStreamLayout viterbi_stream_layout(int streams, int window, int max_states) {
+    ViterbiStreamLayout w{};
+    const size_t row = (size_t)viterbi_row(max_states), slots = (size_t)streams * window;
+    size_t at = 0;
+    w.heads = at; at = align256(at + (size_t)streams * sizeof(ViterbiHead));
+    w.d = at; at = align256(at + (size_t)streams * row * sizeof(float));
+    w.anc = at; at = align256(at + (size_t)streams * row * sizeof(uint16_t));
+    w.back = at; at = align256(at + slots * row);
+    w.kept = at; at = align256(at + slots * PREP * sizeof(float));
+    w.labels = at; at = align256(at + slots * sizeof(int));
+    w.verdict = at; at = align256(at + (size_t)streams * sizeof(int));
+    w.bytes = at;
+    return w;
+}
+
+// what a stream may be asked to take; everything else gets count = -1 and touches nothing
+__device__ __forceinline__ bool viterbi_pushable(const ViterbiHead& head, int T, int frames, int window) {
+    return head.graph >= 0 && pushable(T, frames, head.position, head.commit, window);
+}
+
+// The graph of a stream as the live kernels take it from the caller's arrays: S inside [1, row] whatever they hold.
+struct ViterbiGraph {
+    int first, S, arc0, count;
+    const int* begin;                         // arc_begin of the graph's state 0
+};
+__device__ __forceinline__ ViterbiGraph graph_of(int g, int row, const int* __restrict__ state_begin,
+                                                 const int* __restrict__ arc_begin) {
+    ViterbiGraph out;
+    out.first = state_begin[g];
+    out.S = min(max(state_begin[g + 1] - out.first, 1), row);
+    out.begin = arc_begin + out.first;
+    out.arc0 = out.begin[0];
+    out.count = out.begin[out.S] - out.arc0;
+    return out;
+}
+
+// What viterbi_states tells the live programme at every frame: the ancestors at the commit point move along `from`.
+template <bool Held>
+struct ViterbiAncestors {
+    const ViterbiArcs<Held>& arcs;
+    const uint16_t* before; uint16_t* now;    // anc of frame t-1 and of frame t (LDS)
+    bool fresh; int S;                        // frame t is the commit point: every state is its own ancestor
+    template <int G>
+    __device__ __forceinline__ void operator()(int n0, const int (&meta)[G], const int (&from)[G]) const {
+        uint16_t a[G];
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            int source = n0 + k;
+            if (from[k]) {
+                float weight;
+                arcs.get(first_arc(meta[k]) + from[k] - 1, source, weight);
+                source = min(max(source, 0), S - 1);
+            }
+            a[k] = fresh ? (uint16_t)(n0 + k) : before[source];
+        }
+        if constexpr (G == 4) {
+            *reinterpret_cast<uint2*>(now + n0) = make_uint2((uint32_t)a[0] | (uint32_t)a[1] << 16,
+                                                             (uint32_t)a[2] | (uint32_t)a[3] << 16);
+        } else {
+            now[n0] = a[0];
+        }
+    }
+};
+
+// grid (streams), 64 threads, `held` * 8 bytes of dynamic LDS; G and `row` as for viterbi_programme
+template <int G>
+__global__ __launch_bounds__(64) void viterbi_stream_programme(const float* __restrict__ logp, int frames,
+                                                                const int* __restrict__ lengths, int window,
+                                                                const ViterbiHead* __restrict__ heads,
+                                                                const int* __restrict__ state_begin,
+                                                                const int* __restrict__ phonemes,
+                                                                const float* __restrict__ stay,
+                                                                const float* __restrict__ initial,
+                                                                const int* __restrict__ arc_begin,
+                                                                const int* __restrict__ sources,
+                                                                const float* __restrict__ weights, int held, int row,
+                                                                float* __restrict__ state_d,
+                                                                uint16_t* __restrict__ state_anc,
+                                                                uint8_t* __restrict__ back, float4* __restrict__ kept)
+{
+    __shared__ float4 stage[2][CHUNK_VEC];
+    __shared__ __attribute__((aligned(16))) float dist[2][VSTATES];
+    __shared__ __attribute__((aligned(16))) ViterbiTable table;
+    __shared__ __attribute__((aligned(16))) uint16_t anc[2][VSTATES];
+    extern __shared__ uint2 held_arcs[];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const ViterbiHead head = heads[item];
+    const int T = lengths[item], p = head.position, c = head.commit;
+    if (!viterbi_pushable(head, T, frames, window) || T == 0) return;  // (uniform) refused, or it sits out the step
+    const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
+    float4* ring = kept + (size_t)item * window * PREP_VEC;
+    const int slot0 = p % window;
+    for (int idx = lane; idx < T * PREP_VEC; idx += 64) {      // T <= window: a slot wraps once at most
+        int slot = slot0 + idx / PREP_VEC;
+        slot = slot >= window ? slot - window : slot;
+        ring[(size_t)slot * PREP_VEC + idx % PREP_VEC] = src[idx];
+    }
+    const ViterbiGraph graph = graph_of(head.graph, row, state_begin, arc_begin);
+    const int first = graph.first, S = graph.S, arc0 = graph.arc0, count = graph.count;
+    const int covered = (S + 64 * G - 1) / (64 * G) * (64 * G);    // whole passes: <= row <= VSTATES
+    float* live_d = state_d + (size_t)item * row;
+    uint16_t* live_anc = state_anc + (size_t)item * row;
+    for (int n = lane; n < covered; n += 64) {
+        const bool state = n < S;
+        table.meta[n] = state ? (graph.begin[n] - arc0) | (graph.begin[n + 1] - graph.begin[n]) << 16 |
+                                phonemes[first + n] << 24 : 0;
+        table.stay[n] = state ? stay[first + n] : -INFINITY;
+        dist[(p & 1) ^ 1][n] = live_d[n];                      // D of frame p-1 (-inf at p = 0, and unused there)
+        anc[(p & 1) ^ 1][n] = live_anc[n];
+    }
+    const bool keep = count <= held;                           // (uniform)
+    if (keep)
+        for (int i = lane; i < count; i += 64)
+            held_arcs[i] = make_uint2((uint32_t)min(max(sources[arc0 + i], 0), S - 1),
+                                      __float_as_uint(weights[arc0 + i]));
+    uint8_t* out = back + (size_t)item * window * row;
+    const ViterbiArcs<true> in_lds{held_arcs, nullptr, nullptr, count};
+    const ViterbiArcs<false> in_memory{nullptr, sources + arc0, weights + arc0, count};
+    float4 next[FETCH];
+    fetch(src, 0, T, lane, next);
+    stash(stage[0], lane, next);
+    __syncthreads();
+    int buf = 0, slot = slot0;
+    for (int t0 = 0; t0 < T; t0 += CHUNK, buf ^= 1) {
+        fetch(src, t0 + CHUNK, T, lane, next);
+        const float* e = reinterpret_cast<const float*>(stage[buf]);
+        const int chunk = min(CHUNK, T - t0);
+        for (int u = 0; u < chunk; ++u) {
+            const int t = p + t0 + u;                          // the absolute frame
+            uint8_t* bytes = out + (size_t)slot * row;
+            for (int n0 = lane * G; n0 < covered; n0 += 64 * G) {  // (uniform: every lane takes every pass)
+                if (keep)
+                    viterbi_states<G, true>(t, n0, S, e + u * PREP, table, initial + first, in_lds, dist[(t & 1) ^ 1],
+                                            dist[t & 1], bytes,
+                                            ViterbiAncestors<true>{in_lds, anc[(t & 1) ^ 1], anc[t & 1], t == c, S});
+                else
+                    viterbi_states<G, false>(t, n0, S, e + u * PREP, table, initial + first, in_memory,
+                                             dist[(t & 1) ^ 1], dist[t & 1], bytes,
+                                             ViterbiAncestors<false>{in_memory, anc[(t & 1) ^ 1], anc[t & 1], t == c, S});
+            }
+            slot = slot + 1 == window ? 0 : slot + 1;
+            __syncthreads();                                   // frame t+1 reads what this frame wrote
+        }
+        stash(stage[buf ^ 1], lane, next);                     // its readers passed the barrier above
+        __syncthreads();
+    }
+    const int last = (p + T - 1) & 1;
+    for (int n = lane; n < covered; n += 64) {
+        live_d[n] = dist[last][n];
+        live_anc[n] = anc[last][n];
+    }
+}
+
+// A wave-uniform pointer kept in vector registers: the commit and the flush run out of scalar registers, and these
+// pointers are only ever the address of a vector load or store.
+template <class T>
+__device__ __forceinline__ T* in_vector_registers(T* pointer) {
+    asm volatile("" : "+v"(pointer));
+    return pointer;
+}
+
+// a pointer known to point into LDS: 32 bits, no flat access.  (As a flat pointer in a struct it drew "Illegal
+// instruction detected: Operand has incorrect register class" from the compiler for these kernels.)
+#define PPG_LDS __attribute__((address_space(3)))
+
+// What the commit and the flush of one stream share: the graph's arcs for turning an ordinal into its source state,
+// and the stream's ring of back-pointer rows, of which a refill of VROWS_VEC pieces holds `span` frames, the graph's
+// own `covered` bytes of each.
+constexpr int VPER = VROWS_VEC / 64;          // pieces of a refill per lane
+struct ViterbiLive {
+    int lane, S, covered, count, arc0;
+    bool keep;
+    const PPG_LDS uint16_t* first;            // a state's first arc, counted from the graph's first
+    const PPG_LDS int* held_sources;          // the arcs' sources, clamped, if keep
+    const int* sources;
+    const uint8_t* back;                      // the stream's ring
+    int window, row, per, span;
+    int frame[VPER];                          // the frame of a refill this lane's piece u lies in: (u * 64 + lane) / per
+
+    // the state in-arc from - 1 of state n comes from: inside [0, S) whatever the arrays hold
+    __device__ __forceinline__ int source_of(int n, int from) const {
+        if (count <= 0) return n;
+        const int arc = min((int)first[n] + from - 1, count - 1);
+        return min(max(keep ? held_sources[arc] : sources[arc0 + arc], 0), S - 1);
+    }
+    __device__ __forceinline__ int before(int n, int from) const { return from ? source_of(n, from) : n; }
+
+    // the rows of the frames chunk * span ..., those in [low, high] only
+    __device__ __forceinline__ void load(int chunk, int low, int high, uint4 (&next)[VPER]) const {
+        const uint4* src = reinterpret_cast<const uint4*>(back);
+        const int base = chunk * span, start = base % window;
+#pragma unroll
+        for (int u = 0; u < VPER; ++u) {
+            // (relative to the refill's first frame: a position may be INT32_MAX; span <= window: a slot wraps once)
+            const int at = frame[u];
+            int slot = start + at;
+            slot = slot >= window ? slot - window : slot;
+            next[u] = at < span && at >= low - base && at <= high - base
+                          ? src[(size_t)slot * (row / 16) + u * 64 + lane - at * per] : make_uint4(0, 0, 0, 0);
+        }
+    }
+
+    // body(u, the bytes of frame u's row) for the frames from `start` to `stop`, descending if Down, until it returns
+    // false.  The refills go through `rows`, the next one in flight.  Wave-uniform: so must the body's answer be.
+    template <bool Down, class Body>
+    __device__ __forceinline__ void walk(int start, int stop, uint4 (&rows)[VROWS_VEC], Body&& body) const {
+        if (Down ? start < stop : start > stop) return;        // (uniform)
+        const int low = Down ? stop : start, high = Down ? start : stop;
+        uint4 next[VPER];
+        int chunk = start / span;
+        const int last = stop / span;
+        load(chunk, low, high, next);
+        bool go = true;
+        while (go) {
+            __syncthreads();                                   // the walk over the previous refill is over
+#pragma unroll
+            for (int u = 0; u < VPER; ++u) rows[u * 64 + lane] = next[u];
+            __syncthreads();
+            const bool more = chunk != last;
+            if (more) load(Down ? chunk - 1 : chunk + 1, low, high, next);
+            const PPG_LDS uint8_t* bytes = (const PPG_LDS uint8_t*)rows;
+            const int base = chunk * span;
+            const int bottom = max(low - base, 0), top = min(high - base, span - 1);
+            if (Down) {
+                for (int r = top; go && r >= bottom; --r) go = body(base + r, bytes + r * covered);
+            } else {
+                for (int r = bottom; go && r <= top; ++r) go = body(base + r, bytes + r * covered);
+            }
+            if (!more) break;
+            chunk += Down ? -1 : 1;
+        }
+        __syncthreads();
+    }
+
+    // the labels of the frames [c, fresh) along the path that is in state n at frame `top` >= fresh - 1: the state and
+    // VPARITY where the frame opens a run.  Returns the path's state at frame fresh - 1.  Lane 0 writes.
+    __device__ __forceinline__ int label(int n, int top, int c, int fresh, int* __restrict__ labels,
+                                         uint4 (&rows)[VROWS_VEC]) const {
+        int goal = n;
+        walk<true>(top, c, rows, [&](int u, const PPG_LDS uint8_t* bytes) __attribute__((always_inline)) {
+            const int from = bytes[n];                         // the same address in every lane (frame 0's byte is 0)
+            if (u < fresh && lane == 0) labels[u % window] = n | (from || u == 0 ? VPARITY : 0);
+            if (u == fresh - 1) goal = n;
+            if (u > c) n = before(n, from);
+            return true;
+        });
+        return goal;
+    }
+};
+
+// fills `live` and the LDS tables it points to; a barrier must follow before they are read
+__device__ __forceinline__ ViterbiLive live_of(const ViterbiGraph& graph, const int* __restrict__ sources, int held,
+                                               int row, int window, const uint8_t* back, PPG_LDS uint16_t* first,
+                                               PPG_LDS int* held_sources, int lane) {
+    ViterbiLive live;
+    live.lane = lane; live.S = graph.S; live.count = graph.count; live.arc0 = graph.arc0;
+    live.covered = row == 64 ? 64 : (graph.S + 255) & ~255;    // what the programme wrote of a row: <= row
+    live.keep = graph.count <= held;
+    live.first = first; live.held_sources = held_sources; live.sources = in_vector_registers(sources);
+    live.back = in_vector_registers(back); live.window = window; live.row = row;
+    live.per = live.covered / 16;
+    live.span = min(VROWS_VEC / live.per, window);             // (no more than `window` frames are ever open)
+#pragma unroll
+    for (int u = 0; u < VPER; ++u) live.frame[u] = (u * 64 + lane) / live.per;
+    for (int n = lane; n < live.covered; n += 64)
+        first[n] = (uint16_t)(n < graph.S ? min(max(graph.begin[n] - graph.arc0, 0), VPARITY - 1) : 0);
+    if (live.keep)
+        for (int i = lane; i < graph.count; i += 64)
+            held_sources[i] = min(max(sources[graph.arc0 + i], 0), graph.S - 1);
+    return live;
+}
+
+// the first of the largest of value(n), n < S (strict >, ascending), wave-uniform: its state; *most is its value
+template <class Value>
+__device__ __forceinline__ int first_largest_state(int S, int lane, float* most, Value&& value) {
+    float sum = -INFINITY;
+    int end = VSTATES;
+    for (int n = lane; n < S; n += 64) {
+        const float f = value(n);
+        if (f > sum || end == VSTATES) { sum = f; end = n; }
+    }
+#pragma unroll
+    for (int step = 1; step < 64; step <<= 1) {
+        const float other = __shfl_xor(sum, step);
+        const int state = __shfl_xor(end, step);
+        const bool better = other > sum || (other == sum && state < end);
+        sum = better ? other : sum;
+        end = better ? state : end;
+    }
+    *most = sum;
+    return end;
+}
+
+// The run outputs of one stream's push or flush, as `Runs` with the states beside the phonemes.
+struct StateRuns {
+    int* states; int* phonemes; int* begin; int* end; float* score; float* gop;    // `cap` slots; gop may be null
+    int cap, count;
+};
+
+__device__ __forceinline__ StateRuns state_runs_of(int item, int cap, int* states, int* phonemes, int* begin, int* end,
+                                                   float* score, float* gop) {
+    const size_t at = (size_t)item * cap;
+    return StateRuns{in_vector_registers(states + at), in_vector_registers(phonemes + at),
+                     in_vector_registers(begin + at), in_vector_registers(end + at), in_vector_registers(score + at),
+                     gop ? in_vector_registers(gop + at) : nullptr, cap, 0};
+}
+
+// the open run ends in front of frame `end`.  Wave-uniform; lane 0 writes.
+__device__ __forceinline__ void close_run(const ViterbiHead& run, int end, const int* __restrict__ sym, StateRuns& out,
+                                          int lane) {
+    if (lane == 0 && out.count < out.cap) {
+        const float count = (float)(end - run.start);
+        out.states[out.count] = run.label;
+        out.phonemes[out.count] = min(max(sym[run.label], 0), NP - 1);
+        out.begin[out.count] = run.start;
+        out.end[out.count] = end;
+        out.score[out.count] = run.sum / count;
+        if (out.gop) out.gop[out.count] = run.below / count;
+    }
+    ++out.count;
+}
+
+// slots at or past the runs written: -1 / NaN
+__device__ __forceinline__ void fill_runs(const StateRuns& out, int lane) {
+    for (int h = min(out.count, out.cap) + lane; h < out.cap; h += 64) {
+        out.states[h] = out.phonemes[h] = out.begin[h] = out.end[h] = -1;
+        out.score[h] = NAN;
+        if (out.gop) out.gop[h] = NAN;
+    }
+}
+
+// The run pass over the newly committed frames c .. fresh-1, whose labels stand in the ring, 64 at a time: lane =
+// frame, a ballot of the frames that open a run, the sums in frame order.  `sym` holds the phonemes of the graph's
+// S states.  Leaves head.commit = fresh.  Wave-uniform.
+__device__ __forceinline__ void give_runs(ViterbiHead& head, int fresh, int window, int S,
+                                          const int* __restrict__ sym, const float* __restrict__ kept,
+                                          const int* __restrict__ labels, StateRuns& out, int lane) {
+    const int c = head.commit, count = fresh - c, slot0 = c % window;
+    for (int k0 = 0; k0 < count; k0 += 64) {                   // (uniform)
+        const int k = k0 + lane;
+        int slot = slot0 + k;
+        slot = slot >= window ? slot - window : slot;
+        int state = 0;
+        bool opening = false;
+        float e = 0.f, top = 0.f;
+        if (k < count) {
+            const int label = labels[slot];
+            state = min(max(label & (VPARITY - 1), 0), S - 1);
+            opening = (label & VPARITY) != 0;
+            e = kept[(size_t)slot * PREP + min(max(sym[state], 0), NP - 1)];
+            top = kept[(size_t)slot * PREP + NP];
+        }
+        const float under = e - top;                           // exactly 0 where the label is the frame's maximum
+        const unsigned long long opens = __ballot(opening);
+        const int here = min(64, count - k0);
+        for (int j = 0; j < here; ++j) {                       // in frame order: every lane keeps the same sums
+            if ((opens >> j) & 1) {
+                if (head.label >= 0) close_run(head, c + k0 + j, sym, out, lane);
+                head.label = __builtin_amdgcn_readlane(state, j);
+                head.start = c + k0 + j;
+                head.sum = head.below = 0.f;
+            }
+            head.sum += from_lane(e, j);
+            head.below += from_lane(under, j);
+        }
+    }
+    head.commit = fresh;
+}
+
+// grid (streams), 64 threads, `held` * 4 bytes of dynamic LDS; after the programme and before the advance: the head
+// still holds the old position.
+__global__ __launch_bounds__(64) void viterbi_stream_commit(int frames, const int* __restrict__ lengths, int window,
+                                                             int max_lag, ViterbiHead* __restrict__ heads,
+                                                             const int* __restrict__ state_begin,
+                                                             const int* __restrict__ state_phonemes,
+                                                             const int* __restrict__ arc_begin,
+                                                             const int* __restrict__ sources, int held, int row,
+                                                             float* __restrict__ state_d,
+                                                             uint16_t* __restrict__ state_anc,
+                                                             const uint8_t* __restrict__ back,
+                                                             const float* __restrict__ kept, int* __restrict__ labels,
+                                                             int cap, int* __restrict__ states,
+                                                             int* __restrict__ phonemes, int* __restrict__ begin,
+                                                             int* __restrict__ end, float* __restrict__ score,
+                                                             float* __restrict__ gop, int* __restrict__ count)
+{
+    __shared__ uint4 rows[VROWS_VEC];
+    __shared__ uint16_t first[VSTATES];
+    __shared__ uint16_t both[2][VSTATES];                      // the set of the walk back; the ancestors of the pass forward
+    extern __shared__ int held_sources[];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const int T = lengths[item];
+    ViterbiHead head = heads[item];
+    if (!viterbi_pushable(head, T, frames, window)) {          // (uniform)
+        if (lane == 0) count[item] = -1;
+        return;
+    }
+    ViterbiHead* my_head = in_vector_registers(heads + item);  // what is written at the end: out of the scalar file now
+    int* my_count = in_vector_registers(count + item);
+    StateRuns out = state_runs_of(item, cap, states, phonemes, begin, end, score, gop);
+    const float* my_kept = in_vector_registers(kept + (size_t)item * window * PREP);
+    const ViterbiGraph graph = graph_of(head.graph, row, state_begin, arc_begin);
+    const int* sym = in_vector_registers(state_phonemes + graph.first);
+    const ViterbiLive live = live_of(graph, sources, held, row, window, back + (size_t)item * window * row,
+                                     (PPG_LDS uint16_t*)first, (PPG_LDS int*)held_sources, lane);
+    __syncthreads();
+    const int S = graph.S, covered = live.covered;
+    PPG_LDS uint16_t* const trail = (PPG_LDS uint16_t*)both;   // side s: trail[s * VSTATES + n]
+    float* d = in_vector_registers(state_d + (size_t)item * row);
+    uint16_t* anc = in_vector_registers(state_anc + (size_t)item * row);
+    int* ring_labels = in_vector_registers(labels + (size_t)item * window);
+    const int p = head.position + T, c = head.commit, t = p - 1;
+    float most;
+    const int best = first_largest_state(S, lane, &most, [&](int n) { return d[n]; });
+    int fresh = c;
+    if (most > -INFINITY && t >= c) {                          // (uniform) some state is alive and frames are open
+        // the alive states' ancestors at c differ, so their paths meet nowhere in [c, t]
+        const int lead = anc[best];
+        bool other = false;
+        for (int n = lane; n < S; n += 64) other |= d[n] > -INFINITY && anc[n] != lead;
+        const bool apart = __any(other);
+        const bool far = p - c > max_lag;
+        if (!apart || far) {                                   // (uniform) else nothing to commit
+            int v = c - 1, meet = best;
+            if (!apart) {
+                // the states of all alive paths at frame u, as flags: back from t until they are one state
+                for (int n = lane; n < covered; n += 64) trail[n] = n < S && d[n] > -INFINITY;
+                __syncthreads();
+                int cur = 0;
+                live.walk<true>(t, c, rows, [&](int u, const PPG_LDS uint8_t* bytes) __attribute__((always_inline)) {
+                    int members = 0, one = -1;
+                    for (int n0 = 0; n0 < covered; n0 += 64) {
+                        const unsigned long long in = __ballot(trail[cur * VSTATES + n0 + lane] != 0);
+                        members += __popcll(in);
+                        if (in && one < 0) one = n0 + __ffsll(in) - 1;
+                    }
+                    if (members == 1) { v = u; meet = one; return false; }
+                    if (u == c) return false;                  // (the ancestors said otherwise: never)
+                    for (int n = lane; n < covered; n += 64) trail[(cur ^ 1) * VSTATES + n] = 0;
+                    __syncthreads();
+                    for (int n = lane; n < covered; n += 64)
+                        if (trail[cur * VSTATES + n]) trail[(cur ^ 1) * VSTATES + live.before(n, bytes[n])] = 1;
+                    __syncthreads();
+                    cur ^= 1;
+                    return true;
+                });
+            }
+            const int natural = v + 1;
+            const bool force = p - natural > max_lag;
+            fresh = force ? p - max_lag : natural;
+            if (force) head.forced += fresh - natural;
+            if (fresh > c) {                                   // (uniform)
+                // from the best state at t if the commit is forced, else from the state the alive paths meet in at v
+                const int goal = live.label(force ? best : meet, force ? t : v, c, fresh, ring_labels, rows);
+                if (fresh <= t) {
+                    // every state's ancestor at the new commit point: a[n] = n there, then a[n] = a[before(n)]
+                    for (int n = lane; n < covered; n += 64) trail[n] = (uint16_t)n;
+                    __syncthreads();
+                    int cur = 0;
+                    live.walk<false>(fresh + 1, t, rows, [&](int u, const PPG_LDS uint8_t* bytes) __attribute__((always_inline)) {
+                        for (int n = lane; n < covered; n += 64)
+                            trail[(cur ^ 1) * VSTATES + n] = trail[cur * VSTATES + live.before(n, bytes[n])];
+                        __syncthreads();
+                        cur ^= 1;
+                        return true;
+                    });
+                    const uint8_t* edge = live.back + (size_t)(fresh % window) * row;      // frame fresh's row
+                    for (int n = lane; n < covered; n += 64) {
+                        const int a = trail[cur * VSTATES + n];
+                        anc[n] = (uint16_t)a;
+                        // forced: the paths that were elsewhere at frame fresh - 1 end
+                        if (force && n < S && live.before(a, edge[a]) != goal) d[n] = -INFINITY;
+                    }
+                } else if (force) {                            // max_lag = 0: only the best state goes on
+                    for (int n = lane; n < S; n += 64)
+                        if (n != goal) d[n] = -INFINITY;
+                }
+            }
+        }
+    }
+    __threadfence_block();
+    __syncthreads();                                           // the labels are there for every lane
+    give_runs(head, fresh, window, S, sym, my_kept, ring_labels, out, lane);
+    if (lane == 0) {
+        *my_head = head;                                       // (the position is the advance's to move)
+        *my_count = out.count;
+    }
+    fill_runs(out, lane);
+}
+
+// grid (ceil(streams / 64)), 64 threads: thread = stream.  The commit has said whether the stream took its frames.
+__global__ __launch_bounds__(64) void viterbi_stream_advance(int streams, const int* __restrict__ lengths,
+                                                              const int* __restrict__ count,
+                                                              ViterbiHead* __restrict__ heads)
+{
+    const int item = blockIdx.x * 64 + threadIdx.x;
+    if (item >= streams) return;
+    if (count[item] >= 0) heads[item].position += lengths[item];
+}
+
+// a stream at frame 0 with the graph `graph`.  Wave-uniform; the lanes write D and the ancestors of a whole row.
+__device__ __forceinline__ void restart(ViterbiHead* head, int graph, float* d, uint16_t* anc, int row, int lane) {
+    for (int n = lane; n < row; n += 64) {
+        d[n] = -INFINITY;
+        anc[n] = (uint16_t)n;
+    }
+    if (lane == 0) *head = ViterbiHead{0, 0, 0, -1, 0, 0.f, 0.f, graph};
+}
+
+// grid (streams), 64 threads, `held` * 4 bytes of dynamic LDS.  A stream `which` leaves out, or one without a graph,
+// gets count = 0, total = NaN, forced = -1; the first keeps its state.
+__global__ __launch_bounds__(64) void viterbi_stream_flush(int window, const int* __restrict__ which,
+                                                            ViterbiHead* __restrict__ heads,
+                                                            const int* __restrict__ state_begin,
+                                                            const int* __restrict__ state_phonemes,
+                                                            const float* __restrict__ final_,
+                                                            const int* __restrict__ arc_begin,
+                                                            const int* __restrict__ sources, int held, int row,
+                                                            float* __restrict__ state_d,
+                                                            uint16_t* __restrict__ state_anc,
+                                                            const uint8_t* __restrict__ back,
+                                                            const float* __restrict__ kept, int* __restrict__ labels,
+                                                            int cap, int* __restrict__ states,
+                                                            int* __restrict__ phonemes, int* __restrict__ begin,
+                                                            int* __restrict__ end, float* __restrict__ score,
+                                                            float* __restrict__ gop, int* __restrict__ count,
+                                                            float* __restrict__ total, int* __restrict__ forced)
+{
+    __shared__ uint4 rows[VROWS_VEC];
+    __shared__ uint16_t first[VSTATES];
+    extern __shared__ int held_sources[];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    StateRuns out = state_runs_of(item, cap, states, phonemes, begin, end, score, gop);
+    ViterbiHead head = heads[item];
+    ViterbiHead* my_head = in_vector_registers(heads + item);  // what is written at the end: out of the scalar file now
+    int* my_count = in_vector_registers(count + item);
+    float* my_total = in_vector_registers(total + item);
+    int* my_forced = in_vector_registers(forced + item);
+    uint16_t* my_anc = in_vector_registers(state_anc + (size_t)item * row);
+    const bool meant = !which || which[item] != 0;
+    // (a head that no open, reset or push of this library left gives nothing out and is reset)
+    const bool sound = head.graph >= 0 && head.commit >= 0 && head.commit <= head.position &&
+                       head.position - head.commit <= window;
+    float* d = in_vector_registers(state_d + (size_t)item * row);
+    float sum = NAN;
+    if (meant && sound) {                                      // (uniform)
+        const ViterbiGraph graph = graph_of(head.graph, row, state_begin, arc_begin);
+        const ViterbiLive live = live_of(graph, sources, held, row, window, back + (size_t)item * window * row,
+                                         (PPG_LDS uint16_t*)first, (PPG_LDS int*)held_sources, lane);
+        __syncthreads();
+        const float* last = in_vector_registers(final_ + graph.first);
+        const int state = first_largest_state(graph.S, lane, &sum, [&](int n) { return d[n] + last[n]; });
+        int* ring_labels = in_vector_registers(labels + (size_t)item * window);
+        const int p = head.position, c = head.commit;
+        int fresh = c;
+        if (sum > -INFINITY && p > c) {                        // (uniform) everything up to p along the best path
+            live.label(state, p - 1, c, p, ring_labels, rows);
+            fresh = p;
+        }
+        __threadfence_block();
+        __syncthreads();                                       // the labels are there for every lane
+        const int* sym = in_vector_registers(state_phonemes + graph.first);
+        give_runs(head, fresh, window, graph.S, sym, in_vector_registers(kept + (size_t)item * window * PREP),
+                  ring_labels, out, lane);
+        if (head.label >= 0) close_run(head, head.commit, sym, out, lane);
+    }
+    if (lane == 0) {
+        *my_count = out.count;
+        *my_total = meant && sound ? sum : NAN;
+        *my_forced = meant && sound ? head.forced : -1;
+    }
+    fill_runs(out, lane);
+    if (meant) restart(my_head, head.graph, d, my_anc, row, lane);
+}
+
+// grid (streams), 64 threads.  Open: every stream starts at frame 0 with graph which[item] (null: graph 0), or with
+// none (-1) if that names no graph or the graph was refused.  Else the streams `which` flags (null: all) start again
+// and keep their graph.
+template <bool Open>
+__global__ __launch_bounds__(64) void viterbi_stream_reset(const int* __restrict__ which, int graphs,
+                                                            const int* __restrict__ verdict,
+                                                            ViterbiHead* __restrict__ heads,
+                                                            float* __restrict__ state_d,
+                                                            uint16_t* __restrict__ state_anc, int row)
+{
+    const int item = blockIdx.x;
+    int graph;
+    if (Open) {
+        const int g = which ? which[item] : 0;
+        graph = (unsigned)g < (unsigned)graphs && verdict[g] != 0 ? g : -1;
+    } else {
+        if (which && which[item] == 0) return;                 // (uniform)
+        graph = heads[item].graph;
+    }
+    restart(heads + item, graph, state_d + (size_t)item * row, state_anc + (size_t)item * row, row, threadIdx.x);
+}
+
 // ---- the rungs the host entries share, in the order every entry takes them.  Each returns PPG_OK or has left its
 // message; nothing is launched before the last of an entry's checks has passed. ----
 
@@ -1975,6 +2628,39 @@ int check_recognize_stream_state(const char* what, const void* state, int stream
                                  PPG_RECOGNIZE_STREAM_MAX_WINDOW);
     if (reinterpret_cast<uintptr_t>(state) % 16)
         return ppg::fail_message(PPG_EINVAL, "%s: the state must be 16-byte aligned", what);
+    return PPG_OK;
+}
+
+bool viterbi_stream_sizes_fine(int streams, int window, int max_states) {
+    return streams > 0 && streams <= PPG_VITERBI_STREAM_MAX_STREAMS && window >= PPG_VITERBI_STREAM_MIN_WINDOW &&
+           window <= PPG_VITERBI_STREAM_MAX_WINDOW && window % 64 == 0 && max_states > 0 &&
+           max_states <= PPG_VITERBI_MAX_STATES;
+}
+
+// the checks every entry of the live Viterbi shares: the state and its geometry
+int check_viterbi_stream_state(const char* what, const void* state, int streams, int window, int max_states) {
+    if (!state) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (!viterbi_stream_sizes_fine(streams, window, max_states))
+        return ppg::fail_message(PPG_EINVAL, "%s: %d streams of a window of %d frames and %d states: 1 to %d streams, a "
+                                 "window that is a multiple of 64 from %d to %d, 1 to %d states", what, streams, window,
+                                 max_states, PPG_VITERBI_STREAM_MAX_STREAMS, PPG_VITERBI_STREAM_MIN_WINDOW,
+                                 PPG_VITERBI_STREAM_MAX_WINDOW, PPG_VITERBI_MAX_STATES);
+    if (reinterpret_cast<uintptr_t>(state) % 16)
+        return ppg::fail_message(PPG_EINVAL, "%s: the state must be 16-byte aligned", what);
+    return PPG_OK;
+}
+
+// the packed graphs of a live Viterbi: as ppg_viterbi takes them, and no more graphs than streams
+int check_stream_graphs(const char* what, int streams, int graphs, int n_states, int n_arcs, int max_states,
+                        const void* sources, const void* weights) {
+    if (graphs <= 0 || n_states <= 0 || n_arcs < 0) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (graphs > streams)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d graphs for %d streams, at most one each", what, graphs, streams);
+    if (n_states < graphs || (long long)n_states > (long long)graphs * max_states ||
+        (long long)n_arcs > (long long)graphs * PPG_VITERBI_MAX_ARCS)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d states and %d arcs cannot be %d graphs of 1 to %d states and at "
+                                 "most %d arcs", what, n_states, n_arcs, graphs, max_states, PPG_VITERBI_MAX_ARCS);
+    if (n_arcs > 0 && (!sources || !weights)) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
     return PPG_OK;
 }
 
@@ -2392,6 +3078,133 @@ int ppg_recognize_stream_flush(int device, void* state, int streams, int window,
                        reinterpret_cast<const uint32_t*>(st + w.back), reinterpret_cast<const float*>(st + w.kept),
                        reinterpret_cast<int*>(st + w.labels), cap, phonemes, begin, end, score, gop, count, total,
                        forced);
+    return launched(what);
+}
+
+size_t ppg_viterbi_stream_state_bytes(int streams, int window, int max_states) {
+    return viterbi_stream_sizes_fine(streams, window, max_states)
+               ? viterbi_stream_layout(streams, window, max_states).bytes : 0;
+}
+
+size_t ppg_viterbi_stream_workspace_bytes(int streams, int frames) {
+    if (streams <= 0 || streams > PPG_VITERBI_STREAM_MAX_STREAMS || frames <= 0 || frames > PPG_VITERBI_MAX_FRAMES)
+        return 0;
+    return prepared_bytes(streams, frames);
+}
+
+int ppg_viterbi_stream_open(int device, void* state, int streams, int window, int graphs, int n_states, int n_arcs,
+                            int max_states, const int32_t* state_begin, const int32_t* state_phonemes,
+                            const float* stay, const float* initial, const float* final_, const int32_t* arc_begin,
+                            const int32_t* sources, const float* weights, const int32_t* which_graph, void* stream) {
+    const char* what = "viterbi_stream_open";
+    if (const int rc = check_viterbi_stream_state(what, state, streams, window, max_states)) return rc;
+    if (const int rc = check_stream_graphs(what, streams, graphs, n_states, n_arcs, max_states, sources, weights))
+        return rc;
+    if (const int rc = check_words(what, {state_begin, state_phonemes, stay, initial, final_, arc_begin},
+                                   {sources, weights, which_graph}))
+        return rc;
+    if (const int rc = select_device(device)) return rc;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const ViterbiStreamLayout w = viterbi_stream_layout(streams, window, max_states);
+    char* st = static_cast<char*>(state);
+    int* verdict = reinterpret_cast<int*>(st + w.verdict);
+    hipLaunchKernelGGL(viterbi_check, dim3(graphs), dim3(64), 0, s, n_states, n_arcs, max_states, state_begin,
+                       state_phonemes, stay, initial, final_, arc_begin, sources, weights, verdict);
+    hipLaunchKernelGGL(viterbi_stream_reset<true>, dim3(streams), dim3(64), 0, s, which_graph, graphs, verdict,
+                       reinterpret_cast<ViterbiHead*>(st + w.heads), reinterpret_cast<float*>(st + w.d),
+                       reinterpret_cast<uint16_t*>(st + w.anc), viterbi_row(max_states));
+    return launched(what);
+}
+
+int ppg_viterbi_stream_reset(int device, void* state, int streams, int window, int max_states, const int32_t* which,
+                             void* stream) {
+    const char* what = "viterbi_stream_reset";
+    if (const int rc = check_viterbi_stream_state(what, state, streams, window, max_states)) return rc;
+    if (const int rc = check_words(what, {}, {which})) return rc;
+    if (const int rc = select_device(device)) return rc;
+    const ViterbiStreamLayout w = viterbi_stream_layout(streams, window, max_states);
+    char* st = static_cast<char*>(state);
+    hipLaunchKernelGGL(viterbi_stream_reset<false>, dim3(streams), dim3(64), 0, static_cast<hipStream_t>(stream), which,
+                       0, static_cast<const int*>(nullptr), reinterpret_cast<ViterbiHead*>(st + w.heads),
+                       reinterpret_cast<float*>(st + w.d), reinterpret_cast<uint16_t*>(st + w.anc),
+                       viterbi_row(max_states));
+    return launched(what);
+}
+
+int ppg_viterbi_stream_push(int device, void* state, int streams, int window, const float* ppg, int frames,
+                            const int32_t* lengths, int graphs, int n_states, int n_arcs, int max_states,
+                            const int32_t* state_begin, const int32_t* state_phonemes, const float* stay,
+                            const float* initial, const float* final_, const int32_t* arc_begin,
+                            const int32_t* sources, const float* weights, int max_lag, int cap, int32_t* states,
+                            int32_t* phonemes, int32_t* begin, int32_t* end, float* score, float* gop, int32_t* count,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "viterbi_stream_push";
+    if (const int rc = check_viterbi_stream_state(what, state, streams, window, max_states)) return rc;
+    if (const int rc = check_stream_graphs(what, streams, graphs, n_states, n_arcs, max_states, sources, weights))
+        return rc;
+    if (const int rc = check_words(what, {ppg, lengths, state_begin, state_phonemes, stay, initial, final_, arc_begin,
+                                          states, phonemes, begin, end, score, count, workspace},
+                                   {sources, weights, gop}))
+        return rc;
+    if (frames < 1 || frames > PPG_VITERBI_MAX_FRAMES)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d frames, must be 1 .. %d", what, frames, PPG_VITERBI_MAX_FRAMES);
+    if (max_lag < 0 || max_lag >= window)
+        return ppg::fail_message(PPG_EINVAL, "%s: max_lag = %d, must be 0 .. window - 1 = %d", what, max_lag,
+                                 window - 1);
+    if (cap < 1) return ppg::fail_message(PPG_EINVAL, "%s: cap = %d, must be at least 1", what, cap);
+    if (const int rc = check_workspace(what, workspace, workspace_bytes, prepared_bytes(streams, frames))) return rc;
+    if (const int rc = select_device(device)) return rc;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const ViterbiStreamLayout w = viterbi_stream_layout(streams, window, max_states);
+    char* st = static_cast<char*>(state);
+    ViterbiHead* heads = reinterpret_cast<ViterbiHead*>(st + w.heads);
+    float* d = reinterpret_cast<float*>(st + w.d);
+    uint16_t* anc = reinterpret_cast<uint16_t*>(st + w.anc);
+    uint8_t* back = reinterpret_cast<uint8_t*>(st + w.back);
+    float* kept = reinterpret_cast<float*>(st + w.kept);
+    float* logp = static_cast<float*>(workspace);
+    const int held = n_arcs < VHELD ? n_arcs : VHELD;         // the arcs a wave keeps in LDS, as in ppg_viterbi
+    const int row = viterbi_row(max_states);
+    hipLaunchKernelGGL(align_prepare, dim3((frames + 63) / 64, streams), dim3(64), 0, s, ppg, frames, lengths, logp);
+    hipLaunchKernelGGL(row == 64 ? viterbi_stream_programme<1> : viterbi_stream_programme<4>, dim3(streams), dim3(64),
+                       (size_t)held * sizeof(uint2), s, logp, frames, lengths, window, heads, state_begin,
+                       state_phonemes, stay, initial, arc_begin, sources, weights, held, row, d, anc, back,
+                       reinterpret_cast<float4*>(kept));
+    hipLaunchKernelGGL(viterbi_stream_commit, dim3(streams), dim3(64), (size_t)held * sizeof(int), s, frames, lengths,
+                       window, max_lag, heads, state_begin, state_phonemes, arc_begin, sources, held, row, d, anc, back,
+                       kept, reinterpret_cast<int*>(st + w.labels), cap, states, phonemes, begin, end, score, gop,
+                       count);
+    hipLaunchKernelGGL(viterbi_stream_advance, dim3((streams + 63) / 64), dim3(64), 0, s, streams, lengths, count,
+                       heads);
+    return launched(what);
+}
+
+int ppg_viterbi_stream_flush(int device, void* state, int streams, int window, int graphs, int n_states, int n_arcs,
+                             int max_states, const int32_t* state_begin, const int32_t* state_phonemes,
+                             const float* stay, const float* initial, const float* final_, const int32_t* arc_begin,
+                             const int32_t* sources, const float* weights, const int32_t* which, int cap,
+                             int32_t* states, int32_t* phonemes, int32_t* begin, int32_t* end, float* score,
+                             float* gop, int32_t* count, float* total, int32_t* forced, void* stream) {
+    const char* what = "viterbi_stream_flush";
+    if (const int rc = check_viterbi_stream_state(what, state, streams, window, max_states)) return rc;
+    if (const int rc = check_stream_graphs(what, streams, graphs, n_states, n_arcs, max_states, sources, weights))
+        return rc;
+    if (const int rc = check_words(what, {state_begin, state_phonemes, stay, initial, final_, arc_begin, states,
+                                          phonemes, begin, end, score, count, total, forced},
+                                   {sources, weights, which, gop}))
+        return rc;
+    if (cap < 1) return ppg::fail_message(PPG_EINVAL, "%s: cap = %d, must be at least 1", what, cap);
+    if (const int rc = select_device(device)) return rc;
+    const ViterbiStreamLayout w = viterbi_stream_layout(streams, window, max_states);
+    char* st = static_cast<char*>(state);
+    const int held = n_arcs < VHELD ? n_arcs : VHELD;
+    hipLaunchKernelGGL(viterbi_stream_flush, dim3(streams), dim3(64), (size_t)held * sizeof(int),
+                       static_cast<hipStream_t>(stream), window, which, reinterpret_cast<ViterbiHead*>(st + w.heads),
+                       state_begin, state_phonemes, final_, arc_begin, sources, held, viterbi_row(max_states),
+                       reinterpret_cast<float*>(st + w.d), reinterpret_cast<uint16_t*>(st + w.anc),
+                       reinterpret_cast<const uint8_t*>(st + w.back), reinterpret_cast<const float*>(st + w.kept),
+                       reinterpret_cast<int*>(st + w.labels), cap, states, phonemes, begin, end, score, gop, count,
+                       total, forced);
     return launched(what);
 }
 

@@ -5,6 +5,7 @@ device index; all arithmetic happens in the HIP library.  There is no CPU or
 eager-PyTorch fallback: if the library is missing or no GPU is visible the
 calls raise.
 """
+import collections
 import ctypes
 import math
 import os
@@ -203,6 +204,26 @@ SYMBOLS = {
         ctypes.c_void_p]),
     'ppg_recognize_stream_flush': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_viterbi_stream_state_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_viterbi_stream_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    'ppg_viterbi_stream_open': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_viterbi_stream_reset': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_viterbi_stream_push': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'ppg_viterbi_stream_flush': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_metrics_state_bytes': (ctypes.c_size_t, []),
@@ -1185,6 +1206,89 @@ def recognize_stream_flush(state, streams, window, final, cap, which=None, want_
             end.data_ptr(), score.data_ptr(), gop.data_ptr() if want_gop else None, count.data_ptr(),
             total.data_ptr(), forced.data_ptr(), torch.cuda.current_stream().cuda_stream))
     return phonemes, begin, end, score, gop, count, total, forced
+
+
+VITERBI_STREAM_MIN_WINDOW = 64       # PPG_VITERBI_STREAM_MIN_WINDOW
+VITERBI_STREAM_MAX_WINDOW = 65536    # PPG_VITERBI_STREAM_MAX_WINDOW
+VITERBI_STREAM_MAX_STREAMS = 65535   # PPG_VITERBI_STREAM_MAX_STREAMS
+
+PackedGraphs = collections.namedtuple('PackedGraphs', [
+    'graphs', 'states', 'arcs', 'max_states', 'state_begin', 'phonemes', 'stay', 'initial', 'final', 'arc_begin',
+    'sources', 'weights'])
+
+
+def _graph_arguments(packed):
+    """The graph arguments of the ppg_viterbi_stream_* entries from a PackedGraphs of device tensors."""
+    return (packed.graphs, packed.states, packed.arcs, packed.max_states, packed.state_begin.data_ptr(),
+            packed.phonemes.data_ptr(), packed.stay.data_ptr(), packed.initial.data_ptr(), packed.final.data_ptr(),
+            packed.arc_begin.data_ptr(), packed.sources.data_ptr() if packed.arcs else None,
+            packed.weights.data_ptr() if packed.arcs else None)
+
+
+def viterbi_stream_state(device, streams, window, packed, which=None):
+    """The device block of a live Viterbi (ppg_viterbi_stream_*), opened: `streams` streams with a ring of `window`
+    frames each over the graphs of `packed` (a PackedGraphs of contiguous int32 / fp32 tensors on `device`), stream i
+    on graph which[i] (a device int32 tensor; None: graph 0).  uint8; its owner passes it to the calls below with the
+    same numbers and the same `packed`."""
+    size = library().ppg_viterbi_stream_state_bytes(streams, window, packed.max_states)
+    if size == 0:
+        raise ValueError(f'a live Viterbi takes 1 to {VITERBI_STREAM_MAX_STREAMS} streams, a window that is a multiple '
+                         f'of 64 from {VITERBI_STREAM_MIN_WINDOW} to {VITERBI_STREAM_MAX_WINDOW} and graphs of 1 to '
+                         f'{VITERBI_MAX_STATES} states, got {streams}, {window} and {packed.max_states}')
+    state = torch.empty((size,), dtype=torch.uint8, device=device)
+    viterbi_stream_open(state, streams, window, packed, which)
+    return state
+
+
+def viterbi_stream_open(state, streams, window, packed, which=None):
+    """ppg_viterbi_stream_open on the current stream: the device checks the graphs and every stream starts at frame 0."""
+    with torch.cuda.device(state.device):
+        _check(library().ppg_viterbi_stream_open(
+            state.device.index, state.data_ptr(), streams, window, *_graph_arguments(packed),
+            which.data_ptr() if which is not None else None, torch.cuda.current_stream().cuda_stream))
+
+
+def viterbi_stream_reset(state, streams, window, max_states, which=None):
+    """ppg_viterbi_stream_reset on the current stream: `which` is None (all) or a device int32 (streams,) of flags."""
+    with torch.cuda.device(state.device):
+        _check(library().ppg_viterbi_stream_reset(
+            state.device.index, state.data_ptr(), streams, window, max_states,
+            which.data_ptr() if which is not None else None, torch.cuda.current_stream().cuda_stream))
+
+
+def viterbi_stream_push(state, window, ppg, lengths, packed, max_lag, cap, workspace, want_gop=True):
+    """ppg_viterbi_stream_push on the current stream: ppg (streams, 40, frames) fp32 and lengths (streams,) int32,
+    contiguous on the state's device; `packed` the graphs the state was opened with; workspace a uint8 tensor there ->
+    states, phonemes, begin, end (streams, cap) int32, score, gop (streams, cap) fp32 (gop None without want_gop) and
+    count (streams,) int32: the runs closed in this push; slots at or past it are -1 / NaN."""
+    device = state.device
+    streams, frames = ppg.shape[0], ppg.shape[2]
+    states = torch.empty((streams, cap), dtype=torch.int32, device=device)
+    phonemes, begin, end, score, gop, count = _run_outputs(device, streams, cap, want_gop)
+    with torch.cuda.device(device):
+        _check(library().ppg_viterbi_stream_push(
+            device.index, state.data_ptr(), streams, window, ppg.data_ptr(), frames, lengths.data_ptr(),
+            *_graph_arguments(packed), max_lag, cap, states.data_ptr(), phonemes.data_ptr(), begin.data_ptr(),
+            end.data_ptr(), score.data_ptr(), gop.data_ptr() if want_gop else None, count.data_ptr(),
+            workspace.data_ptr(), workspace.numel(), torch.cuda.current_stream().cuda_stream))
+    return states, phonemes, begin, end, score, gop, count
+
+
+def viterbi_stream_flush(state, streams, window, packed, cap, which=None, want_gop=True):
+    """ppg_viterbi_stream_flush on the current stream -> the run outputs of viterbi_stream_push, and total fp32 and
+    forced int32 (streams,)."""
+    device = state.device
+    states = torch.empty((streams, cap), dtype=torch.int32, device=device)
+    phonemes, begin, end, score, gop, count = _run_outputs(device, streams, cap, want_gop)
+    total = torch.empty((streams,), dtype=torch.float32, device=device)
+    forced = torch.empty((streams,), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _check(library().ppg_viterbi_stream_flush(
+            device.index, state.data_ptr(), streams, window, *_graph_arguments(packed),
+            which.data_ptr() if which is not None else None, cap, states.data_ptr(), phonemes.data_ptr(),
+            begin.data_ptr(), end.data_ptr(), score.data_ptr(), gop.data_ptr() if want_gop else None,
+            count.data_ptr(), total.data_ptr(), forced.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return states, phonemes, begin, end, score, gop, count, total, forced
 
 
 METRICS_FIXED_POINT = 2.0 ** 32        # the real-valued accumulators of PpgMetricsState count units of 2^-32
