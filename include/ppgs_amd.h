@@ -695,6 +695,69 @@ int ppg_viterbi(int device, const float* ppg, int frames, int items, const int32
                 float* gop, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Posterior decoding over a phoneme graph: the sum over ALL paths of ppg_viterbi's graph where ppg_viterbi takes the best
+ * one (forward-backward).  It gives the log-likelihood of the graph given the recording, the probability that each state
+ * is occupied at each frame, and, collapsed over the states, the 40 phonemes per frame given the graph: a PPG in the
+ * library's own layout.  Not in the reference.
+ *
+ * The graph is ppg_viterbi's: S states, sym, stay, ordered in-arcs (src, w), initial, final, every weight finite or
+ * -inf, and e[t, n] = logp[t][sym[n]] the prepared frame of ppg_align.  With LSE = log sum exp, LSE of nothing = -inf:
+ *   alpha[0, n] = e[0, n] + initial[n]
+ *   t > 0:     alpha[t, n] = e[t, n] + LSE(alpha[t-1, n] + stay[n], alpha[t-1, src[j]] + w[j] for every in-arc j)
+ *   total      = LSE over n of (alpha[T-1, n] + final[n])
+ *   beta[T-1, n] = final[n]
+ *   t < T-1:   beta[t, n] = LSE(stay[n] + e[t+1, n] + beta[t+1, n], w + e[t+1, m] + beta[t+1, m] for every arc n -> m)
+ *   gamma[t, n] = exp(alpha[t, n] + beta[t, n] - Z_t),  Z_t = LSE over n of (alpha[t, n] + beta[t, n])
+ *   post[p, t] = the sum of gamma[t, n] over the states with sym[n] = p   (0 for a phoneme no state carries)
+ * Parallel arcs and arcs n -> n each count as a path of their own, as in ppg_viterbi.  Z_t equals total mathematically;
+ * normalising per frame makes every frame's gamma sum to 1 to rounding.
+ * Arithmetic: fp32 in the log domain.  Every row of alpha is kept less the maxima of the rows before it, and those
+ * maxima are added up in float64; beta the same way (its constants cancel in gamma).  total leaves as float64.  Nothing
+ * is a linear-domain probability: a word penalty of -100 stays a finite path.  -inf + finite = -inf, and an LSE whose
+ * candidates are all -inf is -inf: no NaN arises from weights that are finite or -inf.  The phoneme sums are added in an
+ * order that depends on the graph alone, without atomics: the same call gives the same bits.
+ *
+ * Arguments as ppg_viterbi's, and:
+ *   out_begin       : device int32[n_states + 1]: the out-arcs of state n (an index over all states) are out_begin[n] ..
+ *                     out_begin[n + 1] - 1
+ *   targets         : device int32[n_arcs]: the state an arc goes to, counted inside its own graph
+ *   out_weights     : device fp32[n_arcs]      (targets and out_weights may be NULL if n_arcs is 0)
+ *                     The out lists MUST be the transpose of the in lists: the same arcs, listed by source.  The device
+ *                     cannot cheaply verify that; a wrong transpose gives wrong numbers and never an out-of-range access.
+ *   total           : device float64[items], 8-byte aligned
+ *   post            : device fp32 (items, 40, frames): frames 0 .. T-1 of all 40 rows of item b are written
+ *   occupancy       : NULL, or device fp32 (items, frames, state_stride), state_stride >= max_states: gamma[t, n] at
+ *                     [b, t, n] for t < T and n < S
+ *   workspace       : device memory, 16-byte aligned, at least ppg_posterior_workspace_bytes(items, frames, max_states)
+ *                     bytes: four blocks, each 256-byte aligned: the prepared frames (176 B per frame), the rows of
+ *                     alpha (fp32; 64 per frame if max_states <= 64, else max_states rounded up to 256), their float64
+ *                     shift per frame (alpha[t, n] = row[t][n] + shift[t]), and the verdict on every graph.  One item of
+ *                     65536 frames and 1024 states takes 268 MiB.
+ * The device checks the graphs as ppg_viterbi does, and the out lists by the same rules: out_begin must not decrease
+ * or leave its array, a target must lie in [0, S), a weight must not be NaN or +inf, and a graph's out lists must hold
+ * as many arcs as its in lists.  The in-degree keeps PPG_VITERBI_MAX_DEGREE (the check is shared); the out-degree is
+ * bounded only by PPG_VITERBI_MAX_ARCS per graph.  An item whose graph was refused, whose `which` is outside [0, graphs)
+ * or whose length is outside [1, frames] gets total = NaN and nothing else; an item no path fits gets total = -inf and
+ * nothing else.  Frames at or beyond an item's length are never written.  No input makes a kernel read or write outside
+ * its buffers.
+ * Kernel launches on `stream` only: no allocation, synchronisation or copy; every byte a kernel reads was written by an
+ * earlier kernel of the same call, so the workspace needs no clearing.  Calls with workspaces of their own may run
+ * concurrently on several streams.  A batch equals its singles bit for bit.
+ * PPG_EINVAL, with nothing launched, for what ppg_viterbi refuses so (with PPG_POSTERIOR_MAX_FRAMES in the place of
+ * PPG_VITERBI_MAX_FRAMES), a NULL out_begin, total or post, targets or out_weights NULL with n_arcs > 0, a total that is
+ * not 8-byte aligned, or an occupancy with state_stride < max_states (ppg_posterior_workspace_bytes, which is
+ * host-only, returns 0 for impossible sizes).
+ */
+#define PPG_POSTERIOR_MAX_FRAMES 65536       /* 11 minutes: a row of alpha per frame is kept */
+size_t ppg_posterior_workspace_bytes(int items, int frames, int max_states);
+int ppg_posterior(int device, const float* ppg, int frames, int items, const int32_t* lengths,
+                  int graphs, int n_states, int n_arcs, int max_states, const int32_t* state_begin,
+                  const int32_t* state_phonemes, const float* stay, const float* initial, const float* final_,
+                  const int32_t* arc_begin, const int32_t* sources, const float* weights, const int32_t* out_begin,
+                  const int32_t* targets, const float* out_weights, const int32_t* which, double* total, float* post,
+                  float* occupancy, int state_stride, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Phrase search: where in a recording is a phoneme sequence said, and how well (keyword spotting on posteriorgrams).
  * ppg_align pins its transcript to frame 0 and frame T-1; here the match may start and end at any frame.  Not in the
  * reference.

@@ -73,6 +73,24 @@ are special graphs (`chain_graph`, `model_graph`) and `viterbi` equals them bit 
 Not here: states that emit nothing, N-best lists, minimum durations, more than 1024 states.  The live form is
 `ViterbiStream` (ppg_viterbi_stream_*): `RecognizeStream`'s rules with a state of the graph in the place of a phoneme.
 
+Posterior decoding (`posterior`, ppg_posterior): `viterbi` says which single path is best; `posterior` sums over ALL
+paths of the same graph (forward-backward) and so says how sure that is.  With LSE = log sum exp:
+
+    alpha[0, n] = e[0, n] + initial[n];  alpha[t, n] = e[t, n] + LSE(alpha[t-1, n] + stay[n], alpha[t-1, src[j]] + w[j])
+    total = LSE over n of (alpha[T-1, n] + final[n])                  the log-likelihood of the graph, float64
+    beta[T-1, n] = final[n];  beta[t, n] = LSE(stay[n] + e[t+1, n] + beta[t+1, n], w + e[t+1, m] + beta[t+1, m], n -> m)
+    gamma[t, n] = exp(alpha[t, n] + beta[t, n] - Z_t), Z_t = LSE over n: the probability of state n at frame t
+    phonemes[p, t] = the sum of gamma[t, n] over the states with sym[n] = p
+
+fp32 in the log domain with every row shifted by its maximum and the shifts added up in float64; up to 65536 frames.
+`phonemes` is a PPG in the library's own layout, cleaned by the transcript or the lexicon of the graph.
+
+    graph, word_of = ppgs_amd.alignment.word_loop(lexicon, penalty=2.)
+    path = ppgs_amd.alignment.viterbi(ppg, graph)
+    posterior = ppgs_amd.alignment.posterior(ppg, graph, states=True)
+    sure = ppgs_amd.alignment.run_confidence(path, posterior)                # one number in [0, 1] per run of the path
+Not here: a streaming form, training losses or gradients.
+
 Optional phonemes (`forced(..., optional=flags)`, ppg_align_optional): a speaker pauses between words wherever they
 like, and drops a final consonant or a schwa.  flags[n] lets the path leave phoneme n out:
 
@@ -174,6 +192,7 @@ VITERBI_MAX_FRAMES = engine.VITERBI_MAX_FRAMES
 VITERBI_MAX_STATES = engine.VITERBI_MAX_STATES
 VITERBI_MAX_ARCS = engine.VITERBI_MAX_ARCS
 VITERBI_MAX_DEGREE = engine.VITERBI_MAX_DEGREE
+POSTERIOR_MAX_FRAMES = engine.POSTERIOR_MAX_FRAMES
 
 Alignment = collections.namedtuple('Alignment', ['phonemes', 'starts', 'total', 'score', 'gop'])
 Decoding = collections.namedtuple('Decoding', ['phonemes', 'starts'])
@@ -182,6 +201,7 @@ Graph = collections.namedtuple('Graph', ['phonemes', 'stay', 'offsets', 'sources
 Path = collections.namedtuple('Path', ['states', 'phonemes', 'starts', 'total', 'score', 'gop'])
 Hits = collections.namedtuple('Hits', ['phonemes', 'begin', 'end', 'total', 'mean', 'count', 'curve'])
 Runs = collections.namedtuple('Runs', ['phonemes', 'begin', 'end', 'score', 'gop', 'count', 'total', 'forced'])
+Posterior = collections.namedtuple('Posterior', ['total', 'phonemes', 'states'])
 StateRuns = collections.namedtuple('StateRuns', ('states',) + Runs._fields)
 
 
@@ -906,6 +926,89 @@ def viterbi(ppg, graph, lengths=None, gop=True):
         [states[b, :r] for b, r in enumerate(runs)], [phonemes[b, :r] for b, r in enumerate(runs)],
         [starts[b, :r + 1] for b, r in enumerate(runs)], total, [score[b, :r] for b, r in enumerate(runs)],
         [below[b, :r] for b, r in enumerate(runs)] if gop else None)
+
+
+_TRANSPOSED = collections.OrderedDict()        # id(graph) -> (graph, its out-arc lists): the graph is held, so the id is its own
+_TRANSPOSED_MOST = 64
+
+
+def _transposed(graph):
+    """The out-arc lists of a checked Graph: (offsets (S + 1,) int64, targets (A,) int64, weights (A,)), the in-arcs
+    sorted by source with their order kept (a stable sort), so that the arcs out of state n are offsets[n] ..
+    offsets[n + 1] - 1.  Kept per graph object: a graph is transposed once."""
+    kept = _TRANSPOSED.get(id(graph))
+    if kept is not None and kept[0] is graph:
+        _TRANSPOSED.move_to_end(id(graph))
+        return kept[1]
+    count = graph.phonemes.shape[0]
+    offsets, sources = graph.offsets.to(torch.int64), graph.sources.to(torch.int64)
+    into = torch.repeat_interleave(torch.arange(count, dtype=torch.int64), offsets[1:] - offsets[:-1])
+    order = torch.sort(sources, stable=True).indices
+    out_offsets = torch.cat([torch.zeros(1, dtype=torch.int64), torch.bincount(sources, minlength=count).cumsum(0)])
+    lists = (out_offsets, into[order], graph.weights[order])
+    _TRANSPOSED[id(graph)] = (graph, lists)
+    while len(_TRANSPOSED) > _TRANSPOSED_MOST:
+        _TRANSPOSED.popitem(last=False)
+    return lists
+
+
+def posterior(ppg, graph, lengths=None, states=False):
+    """The sum over all paths of `ppg` through a graph of phoneme states (see the module's text): Posterior(total,
+    phonemes, states).
+
+    `ppg` and `lengths` as `viterbi` takes them, up to 65536 frames; `graph` is anything `viterbi` accepts: a Graph
+    (`graph`, `chain_graph`, `model_graph`, `pronunciations`, `word_loop`) for every item, or for a batch a list of B of
+    them.  total is float64, the log-likelihood of the graph given the recording: 0-d for one utterance, (B,) for a
+    batch.  phonemes is the phoneme posterior given the graph, (40, T) or (B, 40, T) fp32 on the device, a PPG that
+    `distance`, `dtw`, `sparsify` and `edit` take; every frame sums to 1.  states is None, or with states=True the
+    occupancy of every state, (T, S) or (B, T, the largest S of the batch).  An utterance that no path fits has total
+    -inf; its outputs, the frames past an item's length and the states past its graph's are zero.  A batch equals its
+    single calls bit for bit, and the same call gives the same bits."""
+    batched, batch, frames = _ppg(ppg, POSTERIOR_MAX_FRAMES, 'posterior')
+    if not batched and lengths is not None:
+        raise ValueError('lengths go with a batch: slice a single PPG instead')
+    lengths = _lengths(lengths, batch, frames)
+    packed, which = _graph_list(graph, batch if batched else None, 'a batch', 'items')
+    counts, state_begin, arc_begin, joined = _joined_graphs(packed)
+    lists = [_transposed(value) for value in packed]
+    arc_base = arc_begin[state_begin[:-1]]
+    out_begin = torch.cat([out[0][:-1] + arc_base[g] for g, out in enumerate(lists)] + [arc_begin[-1:]])
+    device = core.device_for(None, ppg)
+    x = ppg.to(device)
+    total, phonemes, occupancy = engine.posterior_items(
+        x if batched else x[None], lengths, state_begin, joined('phonemes'), joined('stay'), joined('initial'),
+        joined('final'), arc_begin, joined('sources'), joined('weights'), out_begin,
+        torch.cat([out[1] for out in lists]), torch.cat([out[2] for out in lists]), which, max(counts), states)
+    if not batched:
+        return Posterior(total[0], phonemes[0], occupancy[0] if states else None)
+    return Posterior(total, phonemes, occupancy)
+
+
+def run_confidence(path, posterior):
+    """How sure each run of a `viterbi` Path is, from a Posterior of the same PPG and graph made with states=True: the
+    mean occupancy of the run's state over the run's frames, one number in [0, 1] per run ("how sure is this phoneme
+    here").  One utterance gives (R,) fp32; a batch gives a list of B such tensors."""
+    if posterior.states is None:
+        raise ValueError('run_confidence takes a Posterior made with states=True')
+
+    def one(run_states, starts, occupancy):
+        runs = run_states.shape[0]
+        if runs == 0:
+            return occupancy.new_zeros((0,))
+        starts = starts.to(torch.int64)
+        frames = int(starts[-1])
+        spans = starts[1:] - starts[:-1]
+        state = torch.repeat_interleave(run_states.to(torch.int64), spans)
+        taken = occupancy[torch.arange(frames, device=occupancy.device), state]
+        run = torch.repeat_interleave(torch.arange(runs, device=occupancy.device), spans)
+        return occupancy.new_zeros((runs,)).index_add_(0, run, taken) / spans.to(occupancy.dtype)
+    if isinstance(path.states, (list, tuple)):
+        if posterior.states.dim() != 3 or posterior.states.shape[0] != len(path.states):
+            raise ValueError('the Path and the Posterior are not of one batch')
+        return [one(path.states[b], path.starts[b], posterior.states[b]) for b in range(len(path.states))]
+    if posterior.states.dim() != 2:
+        raise ValueError('the Path is of one utterance and the Posterior of a batch')
+    return one(path.states, path.starts, posterior.states)
 
 
 def _queries(phonemes):

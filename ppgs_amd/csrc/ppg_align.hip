@@ -2715,6 +2715,26 @@ int launched(const char* what) {
 
 }  // namespace
 
+// What ppg_posterior.hip shares with this unit: the prepared frames and the check of the packed graphs'
+// in-arc lists, launched from here so that there is one build of either kernel.
+namespace ppg {
+
+void launch_align_prepare(void* stream, const float* ppg, int frames, int items, const int32_t* lengths, float* logp) {
+    hipLaunchKernelGGL(align_prepare, dim3((frames + 63) / 64, items), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       ppg, frames, lengths, logp);
+}
+
+void launch_viterbi_check(void* stream, int graphs, int n_states, int n_arcs, int max_states,
+                          const int32_t* state_begin, const int32_t* state_phonemes, const float* stay,
+                          const float* initial, const float* final_, const int32_t* arc_begin, const int32_t* sources,
+                          const float* weights, int32_t* verdict) {
+    hipLaunchKernelGGL(viterbi_check, dim3(graphs), dim3(64), 0, static_cast<hipStream_t>(stream), n_states, n_arcs,
+                       max_states, state_begin, state_phonemes, stay, initial, final_, arc_begin, sources, weights,
+                       verdict);
+}
+
+}  // namespace ppg
+
 extern "C" {
 
 size_t ppg_align_workspace_bytes(int items, int frames, int max_phonemes) {

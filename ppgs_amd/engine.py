@@ -175,6 +175,13 @@ SYMBOLS = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'ppg_posterior_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_posterior': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'ppg_search_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'ppg_search': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
@@ -988,6 +995,77 @@ def viterbi_items(ppg, lengths, state_begin, phonemes, stay, initial, final, arc
                 total[at:].data_ptr(), score[at:].data_ptr(), gop[at:].data_ptr() if want_gop else None,
                 workspace.data_ptr(), size, stream))
     return states, labels, starts, runs, total, score, gop
+
+
+POSTERIOR_MAX_FRAMES = 65536     # PPG_POSTERIOR_MAX_FRAMES
+POSTERIOR_WORKSPACE_BYTES = 1 << 30  # a larger batch runs as several calls, each within this much workspace
+
+
+def posterior_items(ppg, lengths, state_begin, phonemes, stay, initial, final, arc_begin, sources, weights, out_begin,
+                    targets, out_weights, which=None, max_states=None, want_states=False):
+    """The sum over all paths of item b = ppg[b, :, :lengths[b]] through graph which[b] (ppg_posterior).  The graphs
+    travel packed as `viterbi_items` takes them, with their out-arc lists beside the in-arc lists: out_begin
+    (states + 1,), targets (counted inside each graph) and out_weights over all arcs, the transpose of the in lists.
+    Nothing of the graphs is checked here: the device checks them, and an item whose graph it refuses, whose `which`
+    names no graph or whose length is impossible has total NaN.  (items, 40, frames) on a GPU -> total (items,)
+    float64, the phoneme posterior (items, 40, frames) fp32 and the state occupancy (items, frames, max_states) fp32
+    (None without want_states).  Frames past an item's length, states past its graph's, and the items without a path
+    (total -inf) or refused (NaN) are zero."""
+    x, lengths = _items(ppg, lengths, 'posterior', POSTERIOR_MAX_FRAMES)
+    items, frames = x.shape[0], x.shape[2]
+    device = x.device
+
+    def words(tensor, dtype, name):
+        tensor = torch.as_tensor(tensor)
+        if tensor.dim() != 1:
+            raise ValueError(f'{name} must be one-dimensional, got {tuple(tensor.shape)}')
+        return tensor.to(device=device, dtype=dtype).contiguous()
+    state_begin, arc_begin = words(state_begin, torch.int32, 'state_begin'), words(arc_begin, torch.int32, 'arc_begin')
+    phonemes, sources = words(phonemes, torch.int32, 'phonemes'), words(sources, torch.int32, 'sources')
+    stay, initial = words(stay, torch.float32, 'stay'), words(initial, torch.float32, 'initial')
+    final, weights = words(final, torch.float32, 'final'), words(weights, torch.float32, 'weights')
+    out_begin, targets = words(out_begin, torch.int32, 'out_begin'), words(targets, torch.int32, 'targets')
+    out_weights = words(out_weights, torch.float32, 'out_weights')
+    graphs, count, arcs = state_begin.shape[0] - 1, phonemes.shape[0], sources.shape[0]
+    if graphs < 1 or count < 1:
+        raise ValueError('posterior takes at least one graph of at least one state')
+    for name, tensor, size in (('stay', stay, count), ('initial', initial, count), ('final', final, count),
+                               ('arc_begin', arc_begin, count + 1), ('weights', weights, arcs),
+                               ('out_begin', out_begin, count + 1), ('targets', targets, arcs),
+                               ('out_weights', out_weights, arcs)):
+        if tensor.shape[0] != size:
+            raise ValueError(f'{name} has {tensor.shape[0]} entries, {size} expected')
+    if max_states is None:
+        max_states = min(VITERBI_MAX_STATES, count)
+    if which is not None:
+        which = [int(v) for v in which]
+        if len(which) != items:
+            raise ValueError(f'{len(which)} graphs named for {items} items')
+        which = torch.tensor(which, dtype=torch.int32).to(device)
+    lengths = torch.tensor(lengths, dtype=torch.int32).to(device)
+    lib = library()
+    bytes_for = lib.ppg_posterior_workspace_bytes
+    one = bytes_for(1, frames, max_states)
+    if one == 0:
+        raise ValueError(f'posterior takes graphs of 1 to {VITERBI_MAX_STATES} states, got max_states = {max_states}')
+    total = torch.empty((items,), dtype=torch.float64, device=device)
+    post = torch.zeros((items, 40, frames), dtype=torch.float32, device=device)
+    states = torch.zeros((items, frames, max_states), dtype=torch.float32, device=device) if want_states else None
+    group = max(1, min(items, VITERBI_MAX_ITEMS, POSTERIOR_WORKSPACE_BYTES // one))
+    size = bytes_for(group, frames, max_states)
+    workspace = torch.empty((size,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for at in range(0, items, group):
+            _check(lib.ppg_posterior(
+                device.index, x[at:].data_ptr(), frames, min(group, items - at), lengths[at:].data_ptr(), graphs, count,
+                arcs, max_states, state_begin.data_ptr(), phonemes.data_ptr(), stay.data_ptr(), initial.data_ptr(),
+                final.data_ptr(), arc_begin.data_ptr(), sources.data_ptr() if arcs else None,
+                weights.data_ptr() if arcs else None, out_begin.data_ptr(), targets.data_ptr() if arcs else None,
+                out_weights.data_ptr() if arcs else None, None if which is None else which[at:].data_ptr(),
+                total[at:].data_ptr(), post[at:].data_ptr(), states[at:].data_ptr() if want_states else None,
+                max_states, workspace.data_ptr(), size, stream))
+    return total, post, states
 
 
 SEARCH_MAX_FRAMES = 262144       # PPG_SEARCH_MAX_FRAMES
