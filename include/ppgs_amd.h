@@ -1053,6 +1053,112 @@ int ppg_viterbi_stream_flush(int device, void* state, int streams, int window, i
                              float* gop, int32_t* count, float* total, int32_t* forced, void* stream);
 
 /*
+ * Fixed-lag posteriors over a graph on a live stream: ppg_posterior (forward-backward) with a bounded look-ahead,
+ * carried across the pushes of a stream on the device.  Not in the reference.
+ *
+ * Graph, emissions e, recurrences, shifts, the LSE and the collapse onto phonemes are ppg_posterior's, unchanged.  A
+ * stream has two parameters, fixed when the state is opened, block = H >= 1 and lag = L >= 0; a position p (frames
+ * received) and an emission point c.  Everything below makes the output independent of how the frames are split into
+ * pushes.
+ *   Forward: ppg_posterior's forward recurrence from absolute frame 0.  The row a[p-1], its maximum and the float64
+ *   shift C live in the state; for any split into pushes every row has the bits ppg_posterior computes for the whole
+ *   recording.
+ *   Blocks: block k is frames [kH, (k+1)H).  It is given out by the first push after which p >= (k+1)H + L.  Its
+ *   backward pass starts at the horizon h_k = (k+1)H + L - 1 with beta = 0 for every state: an open end, `final_` is not
+ *   read.  So every frame is smoothed by at least L and at most L + H - 1 later frames, and what is given out is a
+ *   function of the frames [0, h_k] alone.  After a push c = H * max(0, floor((p - L) / H)).
+ *   With open(g) = g with final = 0 everywhere: block k's post, and its occupancy if asked for, are the columns
+ *   [kH, (k+1)H) of ppg_posterior(ppg[:, :h_k + 1], open(g)), bit for bit.
+ *   Evidence: every push also reports evidence = C[p-1] + LSE over n of a[p-1, n] in float64, the log-likelihood of the
+ *   frames so far: the `total` of ppg_posterior(ppg[:, :p], open(g)), bit for bit (0 while p = 0).
+ *   Flush: one backward pass from p - 1 under the graph's own `final_` down to c gives out the frames [c, p) and total.
+ *   For a recording within PPG_POSTERIOR_MAX_FRAMES these are the columns [c, p) and the total of ppg_posterior(whole,
+ *   g), bit for bit; a recording shorter than H + L comes out of the flush alone.  The stream then starts again at
+ *   frame 0.  A flush of a stream that has received nothing gives count = 0 and total = NaN.
+ *   Dead stream: a frame whose row is all -inf makes the stream dead.  That push and every later one report evidence =
+ *   -inf and count = 0, and no more frames are taken; the flush gives count = 0 and total = -inf, as does a flush in
+ *   which no alive state may end.  Blocks given out by earlier pushes stay given out.
+ *   A stream whose graph was refused or is missing reports count = -1 (evidence NaN) at every push and count = 0, total =
+ *   NaN at the flush.  A stream with (p - c) + lengths[i] > window, a length outside [0, frames] or a position that
+ *   would pass INT32_MAX reports count = -1 (evidence NaN) and keeps its state.
+ * Cost: per block the backward pass walks H + L frames; the L look-ahead frames take the beta recurrence alone, the H
+ * frames of the block the whole step of ppg_posterior's backward pass.  block = 1, lag = 0 is the filtered posterior.
+ *
+ * The caller owns the state (device memory, 16-byte aligned, ppg_posterior_stream_state_bytes(streams, window,
+ * max_states) bytes); there is no handle.  With row = 64 if max_states <= 64, else max_states rounded up to 256: four
+ * blocks, each 256-byte aligned: the head of every stream (40 B: p, p before the last push, the stream's graph or -1, H,
+ * L, dead, the maximum of a[p-1], one spare word, C[p-1] as float64), the ring of rows of a (window * row fp32 per
+ * stream, 4 * row bytes per frame), the ring of prepared frames (176 B per frame) and the verdicts on the graphs (int32,
+ * room for `streams`).
+ *
+ * ppg_posterior_stream_emitted(received, block, lag): host-only, c after `received` frames, or -1 for received < 0,
+ * block < 1 or lag < 0.
+ * ppg_posterior_stream_block(previous, received, block, lag, index): host-only, the first frame of the index-th block
+ * (index from 0) that a push which takes a stream from `previous` to `received` frames gives out, or -1 if it gives out
+ * fewer, or for previous < 0, received < previous, block < 1 or lag < 0.  It is the rule by which the push's launch
+ * (a workgroup per frame and stream) places its workgroups, in 64-bit arithmetic: index * block may pass 2^31.
+ * ppg_posterior_stream_open: the graph arguments are ppg_posterior's packed arrays with their out lists, graphs <=
+ * streams; which_graph is device int32[streams], the graph of every stream, or NULL for graph 0.  It checks every graph
+ * on the device as ppg_posterior does, once, leaves the verdicts in the state, records every stream's graph, H and L and
+ * resets every stream.
+ * ppg_posterior_stream_push and _flush take the graph arrays again and go by the stored verdicts: they MUST be the
+ * arrays, with the same contents, the state was opened with.
+ *   ppg, frames, lengths : device fp32 (streams, 40, frames) and int32[streams], lengths[i] in [0, frames]; frames at or
+ *                     past a stream's length are never read
+ *   post            : device fp32 (streams, 40, cap); occupancy: NULL or device fp32 (streams, cap, state_stride),
+ *                     state_stride >= max_states.  Column j is absolute frame begin[i] + j; columns at or past count[i]
+ *                     are never written.  A push gives out at most frames + H - 1 columns, a flush at most H + L - 1;
+ *                     with a smaller cap the columns at or past cap are dropped and count still counts them.
+ *   begin, count    : device int32[streams]
+ *   evidence, total : device float64[streams], 8-byte aligned
+ *   workspace       : device memory, 16-byte aligned, ppg_posterior_stream_workspace_bytes(streams, frames) bytes: the
+ *                     push's prepared frames
+ * ppg_posterior_stream_reset and _flush take `which`, device int32[streams] flags of the streams meant, or NULL for all;
+ * a stream a flush leaves out gets count = 0 and total = NaN.
+ * Kernel launches on `stream` only: no allocation, synchronisation or copy.  Every byte a kernel reads was written by
+ * open, reset or an earlier kernel of the same sequence of calls.  Every stream's results are a function of that stream
+ * alone; the graphs of at most 64 states and the larger ones run in launches of their own, chosen by the stream's own
+ * graph.
+ * PPG_EINVAL, and nothing launched, for: more than PPG_VITERBI_STREAM_MAX_STREAMS streams, a window that is not a
+ * multiple of 64 in [PPG_VITERBI_STREAM_MIN_WINDOW, PPG_VITERBI_STREAM_MAX_WINDOW], max_states outside
+ * 1 .. PPG_VITERBI_MAX_STATES, graphs outside 1 .. streams, n_states or n_arcs that cannot be (as for ppg_viterbi), block
+ * < 1, lag < 0, block + lag > window, frames outside 1 .. PPG_VITERBI_STREAM_MAX_WINDOW, frames * streams above
+ * PPG_POSTERIOR_STREAM_MAX_PUSH (the blocks of a push are one launch of a workgroup per frame and stream; feed a longer
+ * push in pieces), cap < 1, a state stride below
+ * max_states, a NULL or unaligned (16 bytes for the state and the workspace, 8 for evidence and total, 4 for the others)
+ * state, workspace, input or output, a short workspace.  The four helpers are host-only; the *_bytes helpers return 0
+ * for impossible arguments.
+ */
+#define PPG_POSTERIOR_STREAM_MAX_PUSH 67108863  /* frames * streams of one push: 2^26 - 1 */
+int64_t ppg_posterior_stream_emitted(int64_t received, int block, int lag);
+int64_t ppg_posterior_stream_block(int64_t previous, int64_t received, int block, int lag, int64_t index);
+size_t ppg_posterior_stream_state_bytes(int streams, int window, int max_states);
+size_t ppg_posterior_stream_workspace_bytes(int streams, int frames);
+int ppg_posterior_stream_open(int device, void* state, int streams, int window, int graphs, int n_states, int n_arcs,
+                              int max_states, const int32_t* state_begin, const int32_t* state_phonemes,
+                              const float* stay, const float* initial, const float* final_, const int32_t* arc_begin,
+                              const int32_t* sources, const float* weights, const int32_t* out_begin,
+                              const int32_t* targets, const float* out_weights, const int32_t* which_graph, int block,
+                              int lag, void* stream);
+int ppg_posterior_stream_reset(int device, void* state, int streams, int window, int max_states, const int32_t* which,
+                               void* stream);
+int ppg_posterior_stream_push(int device, void* state, int streams, int window, const float* ppg, int frames,
+                              const int32_t* lengths, int graphs, int n_states, int n_arcs, int max_states,
+                              const int32_t* state_begin, const int32_t* state_phonemes, const float* stay,
+                              const float* initial, const float* final_, const int32_t* arc_begin,
+                              const int32_t* sources, const float* weights, const int32_t* out_begin,
+                              const int32_t* targets, const float* out_weights, int cap, float* post, float* occupancy,
+                              int state_stride, int32_t* begin, int32_t* count, double* evidence, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int ppg_posterior_stream_flush(int device, void* state, int streams, int window, int graphs, int n_states, int n_arcs,
+                               int max_states, const int32_t* state_begin, const int32_t* state_phonemes,
+                               const float* stay, const float* initial, const float* final_, const int32_t* arc_begin,
+                               const int32_t* sources, const float* weights, const int32_t* out_begin,
+                               const int32_t* targets, const float* out_weights, const int32_t* which, int cap,
+                               float* post, float* occupancy, int state_stride, int32_t* begin, int32_t* count,
+                               double* total, void* stream);
+
+/*
  * Frame metrics accumulated on the device: what the reference's `python -m ppgs.evaluate` computes per batch with
  * five metric objects (ppgs/evaluate/metrics.py: Accuracy, CategoricalAccuracy, JensenShannon, TopKAccuracy, Loss,
  * DistanceMatrix), here ONE kernel launch per batch into one device block, no host synchronisation, read once at

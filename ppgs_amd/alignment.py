@@ -89,7 +89,10 @@ fp32 in the log domain with every row shifted by its maximum and the shifts adde
     path = ppgs_amd.alignment.viterbi(ppg, graph)
     posterior = ppgs_amd.alignment.posterior(ppg, graph, states=True)
     sure = ppgs_amd.alignment.run_confidence(path, posterior)                # one number in [0, 1] per run of the path
-Not here: a streaming form, training losses or gradients.
+Not here: training losses or gradients.  The live form is `PosteriorStream` (ppg_posterior_stream_*): the forward pass
+carried across pushes, and every block of `block` frames given out once `lag` more frames have been received, smoothed
+by a backward pass from that horizon with an open end: block k = frames [kH, (k+1)H) is columns [kH, (k+1)H) of
+`posterior(ppg[:, :(k+1)H + L], the graph with final = 0)`, bit for bit, whatever the pushes were.
 
 Optional phonemes (`forced(..., optional=flags)`, ppg_align_optional): a speaker pauses between words wherever they
 like, and drops a final consonant or a schwa.  flags[n] lets the path leave phoneme n out:
@@ -203,6 +206,7 @@ Hits = collections.namedtuple('Hits', ['phonemes', 'begin', 'end', 'total', 'mea
 Runs = collections.namedtuple('Runs', ['phonemes', 'begin', 'end', 'score', 'gop', 'count', 'total', 'forced'])
 Posterior = collections.namedtuple('Posterior', ['total', 'phonemes', 'states'])
 StateRuns = collections.namedtuple('StateRuns', ('states',) + Runs._fields)
+PosteriorFrames = collections.namedtuple('PosteriorFrames', ['phonemes', 'states', 'begin', 'count', 'evidence', 'total'])
 
 
 def _ppg(ppg, most=MAX_FRAMES, what='alignment'):
@@ -1487,6 +1491,225 @@ class ViterbiStream(RecognizeStream):
     @staticmethod
     def _workspace_bytes(streams, frames):
         return engine.library().ppg_viterbi_stream_workspace_bytes(streams, frames)
+
+
+class PosteriorStream:
+    """`posterior` on a live stream: the frames come a few at a time, the forward pass is carried across the pushes on
+    the device, and every block of `block` frames is given out as soon as `lag` more frames have been received.
+
+        sure = ppgs_amd.alignment.PosteriorStream(graph, block=16, lag=16, states=True)
+        pieces = [sure.push(piece) for piece in arriving]        # each (40, k), k >= 0
+        pieces.append(sure.flush())
+        cleaned = ppgs_amd.alignment.joined_frames(pieces)       # (40, T): `posterior`'s PPG with a bounded look-ahead
+
+    `graph` is a Graph for every stream, or with `batch=B` a list of B of them (the same object may stand for several
+    streams and travels once), validated as `viterbi` validates it.  Block k = frames [kH, (k+1)H) is given out by the
+    first push after which the stream has received (k+1)H + L frames, from a backward pass that starts at frame
+    (k+1)H + L - 1 with an open end (the graph's `final` is not read): it is columns [kH, (k+1)H) of `posterior(ppg[:,
+    :(k+1)H + L], the graph with final = 0)`, bit for bit, for every split into pushes.  block = 1, lag = 0 is the
+    filtered posterior.  `window`, a multiple of 64 from 64 to 65536 with block + lag <= window, is the ring of every
+    stream in frames.
+
+    `batch=None` is one stream: push((40, F)).  `batch=B` is B streams side by side: push((B, 40, Fmax), lengths),
+    lengths[b] in [0, Fmax] (None: Fmax each); the padding is never read.  push returns `PosteriorFrames(phonemes,
+    states, begin, count, evidence, total)`: phonemes (40, cap) or (B, 40, cap) fp32 with cap = F + block - 1; states
+    None, or with states=True the occupancy (cap, Smax) or (B, cap, Smax); column j is absolute frame begin + j, count,
+    0-d or (B,), the number of columns given out, the columns at or past it zero; evidence, float64, the
+    log-likelihood of the frames so far (`posterior(ppg[:, :p], the graph with final = 0).total`, bit for bit); total
+    None.  A stream that could not take its frames has count = -1.  A frame that leaves no state alive makes the stream
+    dead: evidence = -inf and count = 0 from then on.  A push longer than window - (block + lag - 1) is fed in pieces
+    of that size whose columns are packed behind one another on the device.  A push of no frames calls nothing (its
+    evidence is NaN: nothing was computed).
+    flush(item=None) gives out the rest, [c, p), under the graph's own `final`, with total (float64) and evidence None:
+    the last columns and the total of `posterior` of the whole recording, bit for bit (within its 65536 frames); it
+    restarts every stream, or stream `item`; the streams it leaves out have count = 0 and total = NaN.  reset(item=None)
+    starts every stream, or that one, again at frame 0.  `position` and `emitted` are host lists, kept without reading
+    the device: the frames each stream has been PUSHED since its last flush or reset, and the emission point that goes
+    with that many.  They are the device's p and c as long as every push was taken; a stream that is dead or answered
+    count = -1 took nothing on the device, so there the lists run ahead until the next flush or reset puts both back to
+    0.  Nothing here waits for the device."""
+
+    def __init__(self, graph, block=16, lag=16, window=1024, batch=None, states=False, device=None):
+        if (isinstance(window, bool) or not isinstance(window, int) or window % 64 or
+                not engine.VITERBI_STREAM_MIN_WINDOW <= window <= engine.VITERBI_STREAM_MAX_WINDOW):
+            raise ValueError(f'window must be a multiple of 64 from {engine.VITERBI_STREAM_MIN_WINDOW} to '
+                             f'{engine.VITERBI_STREAM_MAX_WINDOW} frames, got {window!r}')
+        if isinstance(block, bool) or not isinstance(block, int) or block < 1:
+            raise ValueError(f'block must be a number of frames, at least 1, got {block!r}')
+        if isinstance(lag, bool) or not isinstance(lag, int) or lag < 0:
+            raise ValueError(f'lag must be a number of frames, at least 0, got {lag!r}')
+        if block + lag > window:
+            raise ValueError(f'block + lag must fit the window of {window} frames, got {block} + {lag}')
+        if batch is not None and (isinstance(batch, bool) or not isinstance(batch, int) or
+                                  not 1 <= batch <= engine.VITERBI_STREAM_MAX_STREAMS):
+            raise ValueError(f'batch must be None or 1 to {engine.VITERBI_STREAM_MAX_STREAMS} streams, got {batch!r}')
+        self.block, self.lag, self.window, self.batch, self.states = block, lag, window, batch, bool(states)
+        self._streams = 1 if batch is None else batch
+        self._gpu = device
+        self._position = [0] * self._streams
+        self._state = self._workspace = self._graphs = None
+        self._uniform, self._flags = {}, {}
+        packed, which = _graph_list(graph, batch, 'batch=', 'streams')
+        counts, state_begin, arc_begin, joined = _joined_graphs(packed)
+        lists = [_transposed(value) for value in packed]
+        arc_base = arc_begin[state_begin[:-1]]
+        out_begin = torch.cat([out[0][:-1] + arc_base[g] for g, out in enumerate(lists)] + [arc_begin[-1:]])
+        self._host = engine.PackedOutGraphs(
+            len(packed), sum(counts), int(arc_begin[-1]), max(counts), state_begin.to(torch.int32),
+            joined('phonemes').to(torch.int32), joined('stay').to(torch.float32), joined('initial').to(torch.float32),
+            joined('final').to(torch.float32), arc_begin.to(torch.int32), joined('sources').to(torch.int32),
+            joined('weights').to(torch.float32), out_begin.to(torch.int32),
+            torch.cat([out[1] for out in lists]).to(torch.int32), torch.cat([out[2] for out in lists]).to(torch.float32))
+        self._which_graph = None if which is None else torch.tensor(which, dtype=torch.int32)
+
+    @property
+    def position(self):
+        return list(self._position)
+
+    @property
+    def emitted(self):
+        return [int(engine.library().ppg_posterior_stream_emitted(position, self.block, self.lag))
+                for position in self._position]
+
+    def _ensure(self, tensor=None):
+        """The device side, made at the first call that needs it."""
+        if self._state is None:
+            device = core.device_for(self._gpu, tensor)
+            with torch.cuda.device(device):
+                self._graphs = engine.PackedOutGraphs(*[value.to(device).contiguous() if torch.is_tensor(value) else value
+                                                        for value in self._host])
+                which = None if self._which_graph is None else self._which_graph.to(device)
+                self._state = engine.posterior_stream_state(device, self._streams, self.window, self._graphs,
+                                                            self.block, self.lag, which)
+        return self._state.device
+
+    _which = RecognizeStream._which
+
+    def _frames(self, post, states, begin, count, evidence=None, total=None):
+        def drop(tensor):
+            return tensor if tensor is None or self.batch is not None else tensor[0]
+        return PosteriorFrames(*[drop(tensor) for tensor in (post, states, begin, count, evidence, total)])
+
+    def push(self, ppg, lengths=None):
+        if not torch.is_tensor(ppg) or ppg.dim() != (2 if self.batch is None else 3):
+            raise ValueError(f'a push takes {"(40, frames)" if self.batch is None else f"({self.batch}, 40, frames)"}, '
+                             f'got {tuple(getattr(ppg, "shape", ()))}')
+        if ppg.shape[-2] != config.OUTPUT_CHANNELS:
+            raise ValueError(f'PPG must have {config.OUTPUT_CHANNELS} channels, got {tuple(ppg.shape)}')
+        if self.batch is not None and ppg.shape[0] != self.batch:
+            raise ValueError(f'a push takes {self.batch} streams, got {ppg.shape[0]}')
+        frames = ppg.shape[-1]
+        if lengths is None:
+            own = [frames] * self._streams
+        else:
+            if self.batch is None:
+                raise ValueError('lengths go with a batch of streams: slice a single PPG instead')
+            if torch.is_tensor(lengths):
+                lengths = lengths.detach().cpu().reshape(-1).tolist()
+            own = [int(value) for value in (lengths if isinstance(lengths, (list, tuple)) else [lengths])]
+            if len(own) != self._streams:
+                raise ValueError(f'lengths has {len(own)} entries for {self._streams} streams')
+            for value in own:
+                if not 0 <= value <= frames:
+                    raise ValueError(f'lengths: {value} is outside [0, {frames}]')
+        for position, value in zip(self._position, own):
+            if position + value > 2 ** 31 - 1:
+                raise ValueError(f'a stream takes at most {2 ** 31 - 1} frames between resets, got {position} + {value}')
+        device = self._ensure(ppg)
+        most = self._graphs.max_states
+        cap = max(1, frames + self.block - 1)
+        if frames == 0:
+            return self._frames(
+                torch.zeros((self._streams, 40, 0), dtype=torch.float32, device=device),
+                torch.zeros((self._streams, 0, most), dtype=torch.float32, device=device) if self.states else None,
+                torch.tensor(self.emitted, dtype=torch.int32).to(device),
+                torch.zeros((self._streams,), dtype=torch.int32, device=device),
+                torch.full((self._streams,), math.nan, dtype=torch.float64, device=device))
+        x = ppg.to(device=device, dtype=torch.float32)
+        x = x if self.batch is not None else x[None]
+        piece = self.window - (self.block + self.lag - 1)                # what a stream can always still take
+        piece = max(1, min(piece, engine.POSTERIOR_STREAM_MAX_PUSH // self._streams))
+        whole = None
+        if lengths is not None:                                          # through pinned memory: the copy does not wait
+            whole = torch.tensor(own, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
+        need = engine.library().ppg_posterior_stream_workspace_bytes(self._streams, min(frames, piece))
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty((need,), dtype=torch.uint8, device=device)
+        packed = None
+        for at in range(0, frames, piece):
+            size = min(piece, frames - at)
+            if whole is None:
+                if size not in self._uniform:
+                    if len(self._uniform) >= 64:                         # (a stream pushes a few sizes over and over)
+                        self._uniform.clear()
+                    self._uniform[size] = torch.full((self._streams,), size, dtype=torch.int32, device=device)
+                on_device = self._uniform[size]
+            else:
+                on_device = (whole - at).clamp_(0, size)
+            part = engine.posterior_stream_push(
+                self._state, self.window, x[:, :, at:at + size].contiguous(), on_device, self._graphs,
+                cap if frames <= piece else size + self.block - 1, self._workspace, self.states)
+            if frames <= piece:
+                packed = part
+                break
+            packed = self._pack(packed, part, cap)
+        if frames > piece:                                               # without the slot that took what was past count
+            post, states, begin, count, evidence = packed
+            packed = (post[:, :, :cap], None if states is None else states[:, :cap], begin, count, evidence)
+        self._position = [position + value for position, value in zip(self._position, own)]
+        return self._frames(*packed)
+
+    def _pack(self, packed, part, cap):
+        """The columns of a piece behind those of the pieces before it, on the device: the counts add up (-1 stays), the
+        first piece's begin and the last piece's evidence stand."""
+        post, states, begin, count, evidence = part
+        if packed is None:
+            packed = (post.new_zeros((self._streams, 40, cap + 1)),
+                      None if states is None else states.new_zeros((self._streams, cap + 1, states.shape[2])), begin,
+                      torch.zeros_like(count), evidence)
+        slots = torch.arange(post.shape[2], device=count.device)[None, :]
+        fits = (slots < count[:, None]) & (packed[3][:, None] >= 0)
+        where = torch.where(fits, (packed[3][:, None] + slots).clamp_(max=cap), cap).to(torch.int64)
+        packed[0].scatter_(2, where[:, None, :].expand(-1, 40, -1), post)
+        packed[0][:, :, cap] = 0.
+        if states is not None:
+            packed[1].scatter_(1, where[:, :, None].expand(-1, -1, states.shape[2]), states)
+            packed[1][:, cap] = 0.
+        total = torch.where((packed[3] < 0) | (count < 0), torch.full_like(count, -1), packed[3] + count)
+        return packed[0], packed[1], packed[2], total, evidence
+
+    def flush(self, item=None):
+        which = self._which(item)
+        self._ensure()
+        post, states, begin, count, total = engine.posterior_stream_flush(
+            self._state, self._streams, self.window, self._graphs, max(1, self.block + self.lag - 1), which,
+            self.states)
+        self._position = [0 if item is None or b == item else position for b, position in enumerate(self._position)]
+        return self._frames(post, states, begin, count, None, total)
+
+    def reset(self, item=None):
+        which = self._which(item)
+        self._ensure()
+        engine.posterior_stream_reset(self._state, self._streams, self.window, self._graphs.max_states, which)
+        self._position = [0 if item is None or b == item else position for b, position in enumerate(self._position)]
+
+
+def joined_frames(pieces):
+    """The outputs of the pushes and the flush of a PosteriorStream, in order, as one PPG: the first `count` columns of
+    every piece behind one another, (40, T) for one stream, a list of B such tensors for a batch.  A piece with count < 0
+    (frames the stream could not take) adds nothing.  Host only: this is where the counts are read."""
+    pieces = list(pieces)
+    if not pieces:
+        raise ValueError('joined_frames takes at least one PosteriorFrames')
+    batched = pieces[0].phonemes.dim() == 3
+    counts = [piece.count.reshape(-1).tolist() for piece in pieces]
+    streams = len(counts[0])
+    joined = []
+    for b in range(streams):
+        columns = [(piece.phonemes[b] if batched else piece.phonemes)[:, :max(0, count[b])]
+                   for piece, count in zip(pieces, counts)]
+        joined.append(torch.cat(columns, dim=1))
+    return joined if batched else joined[0]
 
 
 def run_segments(runs, sample_rate=config.SAMPLE_RATE, hopsize=config.HOPSIZE):

@@ -647,6 +647,525 @@ __global__ __launch_bounds__(64) void posterior_backward(const float* __restrict
     }
 }
 
+// ---- fixed-lag posteriors on a live stream (ppg_posterior_stream_*) ----
+//
+// The two passes above carried across the pushes of a stream.  A stream has a position p (frames received), an emission
+// point c, a block H and a lag L.  The forward pass is posterior_forward's from absolute frame 0: the row a[p-1] (in the
+// ring), its maximum m[p-1] and the float64 shift C[p-1] are the state, so every row has the bits posterior_forward
+// writes for the whole recording, whatever the pushes.  Block k = frames [kH, (k+1)H) is given out by the first push
+// after which p >= (k+1)H + L: a backward pass from the horizon h = (k+1)H + L - 1 with beta = 0 for every state (an
+// open end: `final` is not read), beta alone down to the block's last frame, posterior_backward's whole step over the
+// block.  What is given out is columns [kH, (k+1)H) of ppg_posterior(ppg[:, :h+1], the graph with final = 0), bit for
+// bit.  The flush is one backward pass from p - 1 under the graph's own `final` down to c.
+// The caller owns the state: four blocks, each 256-byte aligned: the heads (40 B per stream), the ring of rows of `a`
+// (posterior_row(max_states) floats per frame, slot t % W), the ring of prepared frames (176 B per frame) and one
+// verdict per graph (room for as many graphs as streams).  One wave per stream; G = 1 and G = 4 launches as above, each
+// taking the streams whose own graph is of its size, so a stream's bits never depend on its neighbours.
+//   posterior_stream_reset     opens (graph, H, L per stream from the verdicts) or restarts streams
+//   posterior_stream_forward   copies the push's prepared frames into the ring, walks the forward over them into the
+//                              ring, leaves evidence = C[p-1] + LSE(a[p-1]) and the new head
+//   posterior_stream_backward  the blocks the push completed, a workgroup each; or, as the flush, the rest under `final`
+//   posterior_stream_total     what a flush says of every stream: count, begin and total
+
+struct PosteriorHead {
+    int position, previous;                   // p, and p before the last push: c = posterior_emitted(p) at all times
+    int graph;                                // the stream's graph; -1: refused or missing when the stream was opened
+    int block, lag;                           // H and L
+    int dead;                                 // a frame left no state alive: nothing more is taken
+    float before;                             // m[p-1]
+    int spare;
+    double shift;                             // C[p-1]
+};
+static_assert(sizeof(PosteriorHead) == 40, "the head is 40 bytes");
+
+struct PosteriorStreamLayout {
+    size_t heads, rows, kept, verdict, bytes;                  // byte offsets into the state
+};
+
+// (65535 streams of 65536 frames and 1024 states are 1.8e13 bytes: inside a size_t)
+inline PosteriorStreamLayout posterior_stream_layout(int streams, int window, int max_states) {
+    PosteriorStreamLayout w{};
+    const size_t slots = (size_t)streams * window;
+    size_t at = 0;
+    w.heads = at; at = align256(at + (size_t)streams * sizeof(PosteriorHead));
+    w.rows = at; at = align256(at + slots * posterior_row(max_states) * sizeof(float));
+    w.kept = at; at = align256(at + slots * PREP * sizeof(float));
+    w.verdict = at; at = align256(at + (size_t)streams * sizeof(int));
+    w.bytes = at;
+    return w;
+}
+
+// c after p frames: the blocks whose horizon has been received
+__host__ __device__ inline long long posterior_emitted(long long p, int block, int lag) {
+    return p < lag ? 0 : (p - lag) / block * block;
+}
+
+// The first frame of the `index`-th block that a push from `previous` to `received` frames completes, or -1 if it
+// completes fewer: in 64 bits, since index * block passes 2^31 for arguments the entries accept.
+__host__ __device__ inline long long posterior_block(long long previous, long long received, int block, int lag,
+                                                     long long index) {
+    const long long c = posterior_emitted(previous, block, lag), stop = posterior_emitted(received, block, lag);
+    return index >= 0 && index < (stop - c) / block ? c + index * block : -1;
+}
+
+// The graph of a stream from the caller's arrays, S inside [1, row] whatever they hold; whether it is of G's size.
+template <int G>
+__device__ __forceinline__ bool stream_graph(int g, int row, const int* __restrict__ state_begin, PosteriorItem& it) {
+    it.T = 0;
+    it.first = state_begin[g];
+    it.S = min(max(state_begin[g + 1] - it.first, 1), row);
+    it.covered = (it.S + 64 * G - 1) / (64 * G) * (64 * G);
+    return (it.S <= 64) == (G == 1);
+}
+
+__device__ __forceinline__ void restart(PosteriorHead* head) {
+    head->position = 0; head->previous = 0; head->dead = 0; head->before = 0.f; head->spare = 0; head->shift = 0.;
+}
+
+// grid (ceil(streams / 64)), 64 threads: thread = stream.  Open: stream i starts at frame 0 with graph which[i] (null:
+// graph 0), or with none (-1) if that names no graph or the graph was refused.  Else the streams `which` flags (null:
+// all) start again and keep their graph, H and L.
+template <bool Open>
+__global__ __launch_bounds__(64) void posterior_stream_reset(int streams, const int* __restrict__ which, int graphs,
+                                                              const int* __restrict__ verdict, int block, int lag,
+                                                              PosteriorHead* __restrict__ heads)
+{
+    const int item = blockIdx.x * 64 + threadIdx.x;
+    if (item >= streams) return;
+    if (Open) {
+        const int g = which ? which[item] : 0;
+        const bool fine = (unsigned)g < (unsigned)graphs && verdict[g] != 0;
+        heads[item].graph = fine ? g : -1;
+        heads[item].block = block;
+        heads[item].lag = lag;
+    } else if (which && which[item] == 0) {
+        return;
+    }
+    restart(heads + item);
+}
+
+// LSE over n of (end[n] + final_[n]) (final_ null: + 0) in posterior_forward's order: the maximum, then the sum, states
+// n = lane, lane + 64, ...  False where no state may end.  Call it from wave-uniform control flow.
+__device__ __forceinline__ bool lse_end(const float* __restrict__ end, const float* __restrict__ final_, int S, int lane,
+                                        float& out) {
+    float most = -INFINITY;
+    for (int n = lane; n < S; n += 64) most = fmaxf(most, end[n] + (final_ ? final_[n] : 0.f));
+    most = wave_max(most);
+    if (most == -INFINITY) return false;                       // (uniform)
+    float sum = 0.f;
+    for (int n = lane; n < S; n += 64)
+        sum += __builtin_amdgcn_exp2f((end[n] + (final_ ? final_[n] : 0.f) - most) * LOG2E);
+    sum = wave_sum(sum);
+    out = fmaf(LN2, __builtin_amdgcn_logf(sum), most);
+    return true;
+}
+
+// The prepared frames [t0, t0 + CHUNK) of a stream's ring that lie in [lo, hi), one 16-byte piece per lane and u.  t0 is
+// a multiple of CHUNK and the window one of 2 * CHUNK, so a chunk never wraps.
+__device__ __forceinline__ void fetch_ring(const float4* __restrict__ ring, int window, int t0, int lo, int hi, int lane,
+                                           float4 (&piece)[FETCH]) {
+    const int slot0 = t0 >= 0 ? t0 % window : 0;
+#pragma unroll
+    for (int u = 0; u < FETCH; ++u) {
+        const int idx = u * 64 + lane;
+        const int f = t0 + idx / PREP_VEC;
+        const bool there = idx < CHUNK_VEC && f >= lo && f < hi;
+        piece[u] = there ? ring[(size_t)slot0 * PREP_VEC + idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// grid (streams), 64 threads, `held` * 8 bytes of dynamic LDS.  logp (streams, frames, 44) are the push's prepared
+// frames.  A stream without a graph gets count = -1 from the G = 1 launch, which every push makes; one that cannot take
+// its frames count = -1 too, and keeps its state; a dead one count = 0 and evidence = -inf; every other count = 0, which
+// posterior_stream_backward replaces if a block completed, and its evidence.
+template <int G>
+__global__ __launch_bounds__(64) void posterior_stream_forward(const float* __restrict__ logp, int frames,
+                                                                const int* __restrict__ lengths, int window,
+                                                                PosteriorHead* __restrict__ heads,
+                                                                const int* __restrict__ state_begin,
+                                                                const int* __restrict__ phonemes,
+                                                                const float* __restrict__ stay,
+                                                                const float* __restrict__ initial,
+                                                                const int* __restrict__ arc_begin,
+                                                                const int* __restrict__ sources,
+                                                                const float* __restrict__ weights, int held, int row,
+                                                                float* __restrict__ rows, float4* __restrict__ kept,
+                                                                int* __restrict__ begin_out, int* __restrict__ count,
+                                                                double* __restrict__ evidence)
+{
+    __shared__ float4 stage[2][CHUNK_VEC];
+    __shared__ __attribute__((aligned(16))) float a[2][PSTATES];
+    __shared__ __attribute__((aligned(16))) PosteriorTable table;
+    extern __shared__ uint2 held_arcs[];
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const PosteriorHead head = heads[item];
+    if (head.graph < 0) {                                      // (uniform)
+        if (G == 1 && lane == 0) {
+            begin_out[item] = 0; count[item] = -1; evidence[item] = NAN;
+        }
+        return;
+    }
+    PosteriorItem it;
+    if (!stream_graph<G>(head.graph, row, state_begin, it)) return;    // (uniform) the other launch's
+    const int T = lengths[item], p = head.position, c = (int)posterior_emitted(p, head.block, head.lag);
+    const bool takes = T >= 0 && T <= frames && T <= INT32_MAX - p && T <= window - (p - c);
+    if (head.dead || !takes) {                                 // (uniform)
+        if (lane == 0) {
+            heads[item].previous = p;                          // no block completes
+            begin_out[item] = c;
+            count[item] = head.dead ? 0 : -1;
+            evidence[item] = head.dead ? (double)-INFINITY : (double)NAN;
+        }
+        return;
+    }
+    const int S = it.S, first = it.first, covered = it.covered;
+    const int* begin = arc_begin + first;
+    const int arc0 = begin[0];
+    const int arcs = load_graph<G>(it, lane, begin, sources, weights, phonemes, stay, table, held_arcs, held, a);
+    const bool keep = arcs <= held;                            // (uniform)
+    const PosteriorArcs<true> in_lds{held_arcs, nullptr, nullptr, arcs};
+    const PosteriorArcs<false> in_memory{nullptr, sources + arc0, weights + arc0, arcs};
+    const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
+    float4* ring = kept + (size_t)item * window * PREP_VEC;
+    float* out = rows + (size_t)item * window * row;
+    int slot = p % window;                                     // of frame t
+    for (int idx = lane; idx < T * PREP_VEC; idx += 64) {      // T <= window: a slot wraps once at most
+        int to = slot + idx / PREP_VEC;
+        to = to >= window ? to - window : to;
+        ring[(size_t)to * PREP_VEC + idx % PREP_VEC] = src[idx];
+    }
+    __syncthreads();                                           // the rows stand at -inf
+    if (p > 0) {                                               // a[p-1], every lane the pieces it wrote
+        const float* from = out + (size_t)(slot == 0 ? window - 1 : slot - 1) * row;
+        for (int n0 = lane * G; n0 < covered; n0 += 64 * G) {
+            float v[G];
+            get<G>(from + n0, v);
+            put<G>(a[(p - 1) & 1] + n0, v);
+        }
+    }
+    double shift = head.shift;                                 // C[t-1], then C[t]
+    float before = head.before;                                // m[t-1]
+    float4 next[FETCH];
+    fetch(src, 0, T, lane, next);
+    stash(stage[0], lane, next);
+    __syncthreads();
+    int buf = 0;
+    for (int r0 = 0; r0 < T; r0 += CHUNK, buf ^= 1) {
+        fetch(src, r0 + CHUNK, T, lane, next);
+        const float* e = reinterpret_cast<const float*>(stage[buf]);
+        const int chunk = min(CHUNK, T - r0);
+        for (int u = 0; u < chunk; ++u) {
+            const int t = p + r0 + u;
+            const float* last = a[(t & 1) ^ 1];
+            if (t > 0) shift += (double)before;
+            float most = -INFINITY;
+            for (int n0 = lane * G; n0 < covered; n0 += 64 * G) {  // (uniform: every lane takes every pass)
+                float cur[G], v[G];
+                emissions<G>(e + u * PREP, table, n0, cur);
+                if (t == 0) {                                  // (uniform)
+#pragma unroll
+                    for (int k = 0; k < G; ++k) v[k] = cur[k] + (n0 + k < S ? initial[first + n0 + k] : -INFINITY);
+                } else {
+                    if (keep) lse_states<G, true>(n0, table, in_lds, last, v);
+                    else lse_states<G, false>(n0, table, in_memory, last, v);
+#pragma unroll
+                    for (int k = 0; k < G; ++k) v[k] = cur[k] + (v[k] - before);
+                }
+#pragma unroll
+                for (int k = 0; k < G; ++k) most = fmaxf(most, v[k]);
+                put<G>(a[t & 1] + n0, v);
+                put<G>(out + (size_t)slot * row + n0, v);
+            }
+            slot = slot + 1 == window ? 0 : slot + 1;
+            before = wave_max(most);
+            if (before == -INFINITY) {                         // (uniform) nothing is alive: the stream is dead
+                if (lane == 0) {
+                    heads[item].dead = 1;
+                    heads[item].previous = p;
+                    begin_out[item] = c; count[item] = 0; evidence[item] = (double)-INFINITY;
+                }
+                return;
+            }
+            __syncthreads();                                   // frame t+1 reads what this frame wrote
+        }
+        stash(stage[buf ^ 1], lane, next);                     // its readers passed the barrier above
+        __syncthreads();
+    }
+    float lse = 0.f;
+    if (p + T > 0) lse_end(a[(p + T - 1) & 1], nullptr, S, lane, lse);     // (uniform; alive, so there is one)
+    if (lane == 0) {
+        heads[item].position = p + T;
+        heads[item].previous = p;
+        heads[item].before = before;
+        heads[item].shift = shift;
+        begin_out[item] = c; count[item] = 0;
+        evidence[item] = p + T > 0 ? shift + (double)lse : 0.;
+    }
+}
+
+// grid (streams), 64 threads: what a flush says of every stream, before posterior_stream_backward gives the frames out
+// and posterior_stream_reset starts the streams again.  A stream `which` leaves out (null: none), one without a graph
+// or one that has received nothing: count = 0, total = NaN; a dead one, or one in which no alive state may end: count =
+// 0, total = -inf; every other count = p - c and total = C[p-1] + LSE over n of (a[p-1, n] + final[n]) as
+// posterior_forward adds it up.
+__global__ __launch_bounds__(64) void posterior_stream_total(int window, const int* __restrict__ which,
+                                                              const PosteriorHead* __restrict__ heads,
+                                                              const int* __restrict__ state_begin,
+                                                              const float* __restrict__ final_, int row,
+                                                              const float* __restrict__ rows,
+                                                              int* __restrict__ begin_out, int* __restrict__ count,
+                                                              double* __restrict__ total)
+{
+    const int item = blockIdx.x, lane = threadIdx.x;
+    const PosteriorHead head = heads[item];
+    const int p = head.position;
+    const bool meant = head.graph >= 0 && !(which && which[item] == 0) && p > 0;
+    if (!meant || head.dead) {                                 // (uniform)
+        if (lane == 0) {
+            begin_out[item] = head.graph < 0 ? 0 : (int)posterior_emitted(p, head.block, head.lag);
+            count[item] = 0;
+            total[item] = meant ? (double)-INFINITY : (double)NAN;
+        }
+        return;
+    }
+    PosteriorItem it;
+    stream_graph<1>(head.graph, row, state_begin, it);
+    const int c = (int)posterior_emitted(p, head.block, head.lag);
+    float lse = 0.f;
+    const bool ends = lse_end(rows + ((size_t)item * window + (p - 1) % window) * row, final_ + it.first, it.S, lane,
+                              lse);
+    if (lane == 0) {
+        begin_out[item] = c;
+        count[item] = ends ? p - c : 0;
+        total[item] = ends ? head.shift + (double)lse : (double)-INFINITY;
+    }
+}
+
+// grid (blocks, streams), 64 threads, `held` * 8 bytes of dynamic LDS, after posterior_stream_forward.  Workgroup
+// (k, i) runs the k-th of the blocks that stream i's push completed, if there are so many (a push of F frames completes
+// at most F): the blocks of a push read the rings and nothing of each other.  `post` (streams, 40, cap), `occupancy`
+// NULL or (streams, cap, state_stride): column j is frame begin + j, columns at or past cap or count are never written.
+// Flush (grid (1, streams)), after posterior_stream_total: the streams it left a count for give out [c, p) under
+// `final_`.
+template <int G, bool Flush>
+__global__ __launch_bounds__(64) void posterior_stream_backward(int window,
+                                                                 const PosteriorHead* __restrict__ heads,
+                                                                 const int* __restrict__ state_begin,
+                                                                 const int* __restrict__ phonemes,
+                                                                 const float* __restrict__ stay,
+                                                                 const float* __restrict__ final_,
+                                                                 const int* __restrict__ out_begin,
+                                                                 const int* __restrict__ targets,
+                                                                 const float* __restrict__ out_weights, int held,
+                                                                 int row, const float* __restrict__ rows,
+                                                                 const float4* __restrict__ kept, int cap,
+                                                                 float* __restrict__ post,
+                                                                 float* __restrict__ occupancy, int state_stride,
+                                                                 int* __restrict__ count)
+{
+    constexpr int PASSES = G == 1 ? 1 : PSTATES / 256;
+    __shared__ float4 stage[CHUNK_VEC];
+    __shared__ __attribute__((aligned(16))) float eb[2][PSTATES];  // e + b of a frame; the older one serves as `run`
+    __shared__ __attribute__((aligned(16))) float ab[PSTATES];     // b, then a + b, then exp(a + b - its maximum)
+    __shared__ __attribute__((aligned(16))) PosteriorTable table;
+    __shared__ PosteriorOrder by;
+    __shared__ float sums[NP][PPOST];
+    extern __shared__ uint2 held_arcs[];
+    const int item = blockIdx.y, lane = threadIdx.x;
+    const PosteriorHead head = heads[item];
+    if (head.graph < 0 || head.dead) return;                   // (uniform)
+    PosteriorItem it;
+    if (!stream_graph<G>(head.graph, row, state_begin, it)) return;    // (uniform) the other launch's
+    const int p = head.position;
+    const int S = it.S, first = it.first, covered = it.covered;
+    const float* in = rows + (size_t)item * window * row;
+    int c, lo, top, h;                        // column 0; the frames [lo, top] are given out from the horizon h < p
+    if (Flush) {
+        if (count[item] <= 0) return;                          // (uniform) posterior_stream_total: nothing to give out
+        c = lo = (int)posterior_emitted(p, head.block, head.lag);
+        top = h = p - 1;
+    } else {
+        c = (int)posterior_emitted(head.previous, head.block, head.lag);
+        const int stop = (int)posterior_emitted(p, head.block, head.lag);
+        const long long mine = posterior_block(head.previous, p, head.block, head.lag, blockIdx.x);
+        if (mine < 0) return;                                  // (uniform) the push completed fewer blocks
+        lo = (int)mine;                                        // (< stop <= p: what follows stays inside an int)
+        top = lo + head.block - 1;
+        h = top + head.lag;
+        if (blockIdx.x == 0 && lane == 0) count[item] = stop - c;
+    }
+    const int* begin = out_begin + first;
+    const int arc0 = begin[0];
+    const int arcs = load_graph<G>(it, lane, begin, targets, out_weights, phonemes, stay, table, held_arcs, held, eb);
+    const bool keep = arcs <= held;                            // (uniform)
+    __syncthreads();
+    sort_states(table, S, lane, by);
+    // b at the horizon: the graph's own `final` at the flush, else an open end
+    for (int n0 = lane * G; n0 < covered; n0 += 64 * G) {
+        float v[G];
+#pragma unroll
+        for (int k = 0; k < G; ++k) v[k] = n0 + k < S ? (Flush ? final_[first + n0 + k] : 0.f) : -INFINITY;
+        put<G>(ab + n0, v);
+    }
+    __syncthreads();
+    const PosteriorArcs<true> in_lds{held_arcs, nullptr, nullptr, arcs};
+    const PosteriorArcs<false> in_memory{nullptr, targets + arc0, out_weights + arc0, arcs};
+    const float4* ring = kept + (size_t)item * window * PREP_VEC;
+    float* out = post + (size_t)item * NP * cap;
+    float* out_states = occupancy ? occupancy + (size_t)item * cap * state_stride : nullptr;
+    // the lane's sorted positions, as posterior_backward keeps them
+    constexpr int SPAN = G == 1 ? 1 : PSTATES / 64, GOES_ON = 1 << 15;
+    const int span = (S + 63) / 64;                            // sorted positions per lane: <= SPAN
+    int mine[SPAN];
+#pragma unroll
+    for (int u = 0; u < SPAN; ++u) {
+        const int i = lane * span + u;
+        const bool there = u < span && i < S;
+        const int n = there ? by.order[i] : 0;
+        const bool goes_on = there && u > 0 && table.sym[n] == table.sym[by.order[i - 1]];
+        mine[u] = n | (goes_on ? GOES_ON : 0);
+    }
+    // the lane's own states of a row of `a`, pass by pass, as the forward pass wrote them: the rows from `top` down, one
+    // per call; nothing below the block
+    float ahead[PAHEAD][PASSES][G];
+    int behind = top % window, left = top - lo + 1;            // the slot of the next row to read; rows left
+    auto load_row = [&](float (&to)[PASSES][G]) {
+#pragma unroll
+        for (int q = 0; q < PASSES; ++q) {
+            const int n0 = (q * 64 + lane) * G;
+            if (left > 0 && n0 < covered) get<G>(in + (size_t)behind * row + n0, to[q]);      // (uniform)
+            else
+#pragma unroll
+                for (int k = 0; k < G; ++k) to[q][k] = -INFINITY;
+        }
+        behind = behind == 0 ? window - 1 : behind - 1;
+        --left;
+    };
+#pragma unroll
+    for (int d = 0; d < PAHEAD; ++d) load_row(ahead[d]);
+    float4 next[FETCH];
+    int cidx = h / CHUNK;                                      // the chunk of prepared frames in `stage`
+    fetch_ring(ring, window, cidx * CHUNK, lo, h + 1, lane, next);
+    stash(stage, lane, next);
+    __syncthreads();
+    fetch_ring(ring, window, (cidx - 1) * CHUNK, lo, h + 1, lane, next);
+    float before = 0.f;                                        // the maximum of b[t+1, .]
+    for (int t = h; t >= lo; --t) {
+        const bool whole = t <= top;                           // (uniform) a frame of the block: the full step
+        const float* e = reinterpret_cast<const float*>(stage) + (t - cidx * CHUNK) * PREP;
+        const float* last = eb[(t & 1) ^ 1];
+        float* now = eb[t & 1];
+        float most = -INFINITY;
+        for (int n0 = lane * G; n0 < covered; n0 += 64 * G) {  // (uniform: every lane takes every pass)
+            float cur[G], v[G];
+            emissions<G>(e, table, n0, cur);
+            if (t == h) {                                      // (uniform) b at the horizon, every lane what it wrote
+                get<G>(ab + n0, v);
+            } else {
+                if (keep) lse_states<G, true>(n0, table, in_lds, last, v);
+                else lse_states<G, false>(n0, table, in_memory, last, v);
+#pragma unroll
+                for (int k = 0; k < G; ++k) v[k] -= before;
+            }
+#pragma unroll
+            for (int k = 0; k < G; ++k) most = fmaxf(most, v[k]);
+            if (whole) put<G>(ab + n0, v);
+#pragma unroll
+            for (int k = 0; k < G; ++k) v[k] += cur[k];
+            put<G>(now + n0, v);
+        }
+        before = wave_max(most);                               // (finite: a path exists)
+        if (whole) {
+            const int j = t - c;                               // the column
+            // a + b from the row read ahead (every lane touches only what it wrote), and its maximum
+            float peak = -INFINITY;
+#pragma unroll
+            for (int q = 0; q < PASSES; ++q) {
+                const int n0 = (q * 64 + lane) * G;
+                if (n0 < covered) {                            // (uniform)
+                    float v[G];
+                    get<G>(ab + n0, v);
+#pragma unroll
+                    for (int k = 0; k < G; ++k) {
+                        v[k] += ahead[0][q][k];
+                        peak = fmaxf(peak, v[k]);
+                    }
+                    put<G>(ab + n0, v);
+                }
+            }
+#pragma unroll
+            for (int d = 0; d + 1 < PAHEAD; ++d)
+#pragma unroll
+                for (int q = 0; q < PASSES; ++q)
+#pragma unroll
+                    for (int k = 0; k < G; ++k) ahead[d][q][k] = ahead[d + 1][q][k];
+            load_row(ahead[PAHEAD - 1]);
+            peak = wave_max(peak);
+            peak = peak > -INFINITY ? peak : 0.f;              // (a path exists, so it is finite: no NaN if it were not)
+            float sum = 0.f;
+            for (int n0 = lane * G; n0 < covered; n0 += 64 * G) {
+                float v[G];
+                get<G>(ab + n0, v);
+#pragma unroll
+                for (int k = 0; k < G; ++k) {
+                    v[k] = __builtin_amdgcn_exp2f((v[k] - peak) * LOG2E);
+                    sum += v[k];
+                }
+                put<G>(ab + n0, v);
+            }
+            sum = wave_sum(sum);
+            const float scale = sum > 0.f ? 1.f / sum : 0.f;
+            if (out_states && j < cap) {                       // (uniform)
+                float* to = out_states + (size_t)j * state_stride;
+                for (int n0 = lane * G; n0 < covered; n0 += 64 * G) {
+                    float v[G];
+                    get<G>(ab + n0, v);
+#pragma unroll
+                    for (int k = 0; k < G; ++k)
+                        if (n0 + k < S) to[n0 + k] = v[k] * scale;
+                }
+            }
+            __syncthreads();                                   // ab stands; `last` has been read by every lane
+            float* run = eb[(t & 1) ^ 1];
+            {
+                float x[SPAN];
+#pragma unroll
+                for (int u = 0; u < SPAN; ++u) x[u] = ab[mine[u] & (PSTATES - 1)];     // (all in flight together)
+                float sofar = 0.f;
+#pragma unroll
+                for (int u = 0; u < SPAN; ++u) {               // (no masks: a lane's SPAN slots are its own)
+                    sofar = fmaf(sofar, (float)((mine[u] >> 15) & 1), x[u]);
+                    run[lane * SPAN + u] = sofar;
+                }
+            }
+            __syncthreads();
+            if (lane < NP) {
+                const int i0 = by.from[lane], i1 = by.from[lane + 1];
+                float whole_sum = 0.f;
+                if (i1 > i0)
+                    for (int l = i0 / span; l <= (i1 - 1) / span; ++l)
+                        whole_sum += run[l * SPAN + min(span, i1 - l * span) - 1];
+                sums[lane][j % PPOST] = whole_sum * scale;
+            }
+            __syncthreads();                                   // frame t-1 writes where `run` stood
+            if (j % PPOST == 0 || t == lo) {                   // (uniform) the columns from j on stand, 64 at most
+                const int column = j + lane;
+                if (column <= min(j | (PPOST - 1), top - c) && column < cap)
+#pragma unroll 8
+                    for (int q = 0; q < NP; ++q) out[(size_t)q * cap + column] = sums[q][column % PPOST];
+            }
+        } else {
+            __syncthreads();                                   // frame t-1 reads `now` and writes `last`
+        }
+        if (t == cidx * CHUNK && t > lo) {                     // (uniform) the chunk below, which has been in flight
+            stash(stage, lane, next);
+            __syncthreads();
+            --cidx;
+            fetch_ring(ring, window, (cidx - 1) * CHUNK, lo, h + 1, lane, next);
+        }
+    }
+}
+
 int check_words(const char* what, std::initializer_list<const void*> required,
                 std::initializer_list<const void*> may_be_null) {
     for (const void* pointer : required)
@@ -663,9 +1182,248 @@ bool posterior_sizes_fine(int items, int frames, int max_states) {
            max_states > 0 && max_states <= PPG_VITERBI_MAX_STATES;
 }
 
+bool posterior_stream_sizes_fine(int streams, int window, int max_states) {
+    return streams > 0 && streams <= PPG_VITERBI_STREAM_MAX_STREAMS && window >= PPG_VITERBI_STREAM_MIN_WINDOW &&
+           window <= PPG_VITERBI_STREAM_MAX_WINDOW && window % 64 == 0 && max_states > 0 &&
+           max_states <= PPG_VITERBI_MAX_STATES;
+}
+
+// the checks every entry of the live posterior shares: the state and its geometry
+int check_posterior_stream_state(const char* what, const void* state, int streams, int window, int max_states) {
+    if (!state) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (!posterior_stream_sizes_fine(streams, window, max_states))
+        return ppg::fail_message(PPG_EINVAL, "%s: %d streams of a window of %d frames and %d states: 1 to %d streams, a "
+                                 "window that is a multiple of 64 from %d to %d, 1 to %d states", what, streams, window,
+                                 max_states, PPG_VITERBI_STREAM_MAX_STREAMS, PPG_VITERBI_STREAM_MIN_WINDOW,
+                                 PPG_VITERBI_STREAM_MAX_WINDOW, PPG_VITERBI_MAX_STATES);
+    if (reinterpret_cast<uintptr_t>(state) % 16)
+        return ppg::fail_message(PPG_EINVAL, "%s: the state must be 16-byte aligned", what);
+    return PPG_OK;
+}
+
+// the packed graphs of a live posterior: as ppg_posterior takes them, and no more graphs than streams
+int check_posterior_stream_graphs(const char* what, int streams, int graphs, int n_states, int n_arcs, int max_states,
+                                  const void* sources, const void* weights, const void* targets,
+                                  const void* out_weights) {
+    if (graphs <= 0 || n_states <= 0 || n_arcs < 0) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (graphs > streams)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d graphs for %d streams, at most one each", what, graphs, streams);
+    if (n_states < graphs || (long long)n_states > (long long)graphs * max_states ||
+        (long long)n_arcs > (long long)graphs * PPG_VITERBI_MAX_ARCS)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d states and %d arcs cannot be %d graphs of 1 to %d states and at "
+                                 "most %d arcs", what, n_states, n_arcs, graphs, max_states, PPG_VITERBI_MAX_ARCS);
+    if (n_arcs > 0 && (!sources || !weights || !targets || !out_weights))
+        return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    return PPG_OK;
+}
+
+// the outputs a push and a flush share
+int check_posterior_stream_outputs(const char* what, int cap, const void* occupancy, int state_stride, int max_states,
+                                   const void* float64) {
+    if (cap < 1) return ppg::fail_message(PPG_EINVAL, "%s: cap = %d, must be at least 1", what, cap);
+    if (occupancy && state_stride < max_states)
+        return ppg::fail_message(PPG_EINVAL, "%s: a state stride of %d for graphs of up to %d states", what,
+                                 state_stride, max_states);
+    if (!float64 || reinterpret_cast<uintptr_t>(float64) % 8)
+        return ppg::fail_message(PPG_EINVAL, "%s: evidence and total must be float64, 8-byte aligned", what);
+    return PPG_OK;
+}
+
+// the arcs a wave keeps in LDS beside the backward pass's static 40 KiB: more than a launch gets without asking
+template <bool Flush>
+int allow_posterior_stream_lds(const char* what) {
+    for (const void* kernel : {reinterpret_cast<const void*>(posterior_stream_backward<1, Flush>),
+                               reinterpret_cast<const void*>(posterior_stream_backward<4, Flush>)})
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PHELD * (int)sizeof(uint2)) !=
+            hipSuccess)
+            return ppg::fail_message(PPG_EDEVICE, "%s: the device refuses %d bytes of dynamic LDS", what,
+                                     PHELD * (int)sizeof(uint2));
+    return PPG_OK;
+}
+
+int posterior_stream_launched(const char* what) {
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? PPG_OK : ppg::fail_message(PPG_EDEVICE, "%s: %s", what, hipGetErrorString(he));
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t ppg_posterior_stream_emitted(int64_t received, int block, int lag) {
+    if (received < 0 || block < 1 || lag < 0) return -1;
+    return posterior_emitted(received, block, lag);
+}
+
+int64_t ppg_posterior_stream_block(int64_t previous, int64_t received, int block, int lag, int64_t index) {
+    if (previous < 0 || received < previous || block < 1 || lag < 0) return -1;
+    return posterior_block(previous, received, block, lag, index);
+}
+
+size_t ppg_posterior_stream_state_bytes(int streams, int window, int max_states) {
+    return posterior_stream_sizes_fine(streams, window, max_states)
+               ? posterior_stream_layout(streams, window, max_states).bytes : 0;
+}
+
+size_t ppg_posterior_stream_workspace_bytes(int streams, int frames) {
+    if (streams <= 0 || streams > PPG_VITERBI_STREAM_MAX_STREAMS || frames <= 0 ||
+        frames > PPG_VITERBI_STREAM_MAX_WINDOW)
+        return 0;
+    return align256((size_t)streams * frames * PREP * sizeof(float));
+}
+
+int ppg_posterior_stream_open(int device, void* state, int streams, int window, int graphs, int n_states, int n_arcs,
+                              int max_states, const int32_t* state_begin, const int32_t* state_phonemes,
+                              const float* stay, const float* initial, const float* final_, const int32_t* arc_begin,
+                              const int32_t* sources, const float* weights, const int32_t* out_begin,
+                              const int32_t* targets, const float* out_weights, const int32_t* which_graph, int block,
+                              int lag, void* stream) {
+    const char* what = "posterior_stream_open";
+    if (const int rc = check_posterior_stream_state(what, state, streams, window, max_states)) return rc;
+    if (const int rc = check_posterior_stream_graphs(what, streams, graphs, n_states, n_arcs, max_states, sources,
+                                                     weights, targets, out_weights))
+        return rc;
+    if (block < 1 || lag < 0 || (long long)block + lag > window)
+        return ppg::fail_message(PPG_EINVAL, "%s: block = %d and lag = %d: a block of at least 1 frame, a lag of at "
+                                 "least 0, together at most the window of %d", what, block, lag, window);
+    if (const int rc = check_words(what, {state_begin, state_phonemes, stay, initial, final_, arc_begin, out_begin},
+                                   {sources, weights, targets, out_weights, which_graph}))
+        return rc;
+    if (hipSetDevice(device) != hipSuccess)
+        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const PosteriorStreamLayout w = posterior_stream_layout(streams, window, max_states);
+    char* st = static_cast<char*>(state);
+    int* verdict = reinterpret_cast<int*>(st + w.verdict);
+    ppg::launch_viterbi_check(stream, graphs, n_states, n_arcs, max_states, state_begin, state_phonemes, stay, initial,
+                              final_, arc_begin, sources, weights, verdict);
+    hipLaunchKernelGGL(posterior_check, dim3(graphs), dim3(64), 0, s, n_arcs, state_begin, arc_begin, out_begin,
+                       targets, out_weights, verdict);
+    hipLaunchKernelGGL(posterior_stream_reset<true>, dim3((streams + 63) / 64), dim3(64), 0, s, streams, which_graph,
+                       graphs, verdict, block, lag, reinterpret_cast<PosteriorHead*>(st + w.heads));
+    return posterior_stream_launched(what);
+}
+
+int ppg_posterior_stream_reset(int device, void* state, int streams, int window, int max_states, const int32_t* which,
+                               void* stream) {
+    const char* what = "posterior_stream_reset";
+    if (const int rc = check_posterior_stream_state(what, state, streams, window, max_states)) return rc;
+    if (const int rc = check_words(what, {}, {which})) return rc;
+    if (hipSetDevice(device) != hipSuccess)
+        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    const PosteriorStreamLayout w = posterior_stream_layout(streams, window, max_states);
+    char* st = static_cast<char*>(state);
+    hipLaunchKernelGGL(posterior_stream_reset<false>, dim3((streams + 63) / 64), dim3(64), 0,
+                       static_cast<hipStream_t>(stream), streams, which, 0, static_cast<const int*>(nullptr), 0, 0,
+                       reinterpret_cast<PosteriorHead*>(st + w.heads));
+    return posterior_stream_launched(what);
+}
+
+int ppg_posterior_stream_push(int device, void* state, int streams, int window, const float* ppg, int frames,
+                              const int32_t* lengths, int graphs, int n_states, int n_arcs, int max_states,
+                              const int32_t* state_begin, const int32_t* state_phonemes, const float* stay,
+                              const float* initial, const float* final_, const int32_t* arc_begin,
+                              const int32_t* sources, const float* weights, const int32_t* out_begin,
+                              const int32_t* targets, const float* out_weights, int cap, float* post, float* occupancy,
+                              int state_stride, int32_t* begin, int32_t* count, double* evidence, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    const char* what = "posterior_stream_push";
+    if (const int rc = check_posterior_stream_state(what, state, streams, window, max_states)) return rc;
+    if (const int rc = check_posterior_stream_graphs(what, streams, graphs, n_states, n_arcs, max_states, sources,
+                                                     weights, targets, out_weights))
+        return rc;
+    if (const int rc = check_words(what, {ppg, lengths, state_begin, state_phonemes, stay, initial, final_, arc_begin,
+                                          out_begin, post, begin, count, workspace},
+                                   {sources, weights, targets, out_weights, occupancy}))
+        return rc;
+    if (frames < 1 || frames > PPG_VITERBI_STREAM_MAX_WINDOW)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d frames, must be 1 .. %d", what, frames,
+                                 PPG_VITERBI_STREAM_MAX_WINDOW);
+    if ((long long)frames * streams > PPG_POSTERIOR_STREAM_MAX_PUSH)  // a workgroup per frame and stream: one launch
+        return ppg::fail_message(PPG_EINVAL, "%s: %d frames for %d streams, at most %d frames x streams a push", what,
+                                 frames, streams, PPG_POSTERIOR_STREAM_MAX_PUSH);
+    if (const int rc = check_posterior_stream_outputs(what, cap, occupancy, state_stride, max_states, evidence))
+        return rc;
+    const size_t need = align256((size_t)streams * frames * PREP * sizeof(float));
+    if (workspace_bytes < need)
+        return ppg::fail_message(PPG_EINVAL, "%s: workspace of %zu bytes, %zu needed", what, workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16)
+        return ppg::fail_message(PPG_EINVAL, "%s: workspace must be 16-byte aligned", what);
+    if (hipSetDevice(device) != hipSuccess)
+        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    if (const int rc = allow_posterior_stream_lds<false>(what)) return rc;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const PosteriorStreamLayout w = posterior_stream_layout(streams, window, max_states);
+    char* st = static_cast<char*>(state);
+    PosteriorHead* heads = reinterpret_cast<PosteriorHead*>(st + w.heads);
+    float* rows = reinterpret_cast<float*>(st + w.rows);
+    float4* kept = reinterpret_cast<float4*>(st + w.kept);
+    float* logp = static_cast<float*>(workspace);
+    const int row = posterior_row(max_states);
+    const int held = n_arcs < PHELD ? n_arcs : PHELD;         // the arcs a wave keeps in LDS, sized by the call
+    const size_t lds = (size_t)held * sizeof(uint2);
+    ppg::launch_align_prepare(stream, ppg, frames, streams, lengths, logp);
+    // the streams whose graph has at most 64 states, then, if the state may hold any, the larger ones
+    hipLaunchKernelGGL(posterior_stream_forward<1>, dim3(streams), dim3(64), lds, s, logp, frames, lengths, window,
+                       heads, state_begin, state_phonemes, stay, initial, arc_begin, sources, weights, held, row, rows,
+                       kept, begin, count, evidence);
+    if (row > 64)
+        hipLaunchKernelGGL(posterior_stream_forward<4>, dim3(streams), dim3(64), lds, s, logp, frames, lengths, window,
+                           heads, state_begin, state_phonemes, stay, initial, arc_begin, sources, weights, held, row,
+                           rows, kept, begin, count, evidence);
+    // a push of `frames` frames completes at most as many blocks: a workgroup each, most of which leave at once
+    hipLaunchKernelGGL((posterior_stream_backward<1, false>), dim3(frames, streams), dim3(64), lds, s, window, heads,
+                       state_begin, state_phonemes, stay, final_, out_begin, targets, out_weights, held, row, rows, kept,
+                       cap, post, occupancy, state_stride, count);
+    if (row > 64)
+        hipLaunchKernelGGL((posterior_stream_backward<4, false>), dim3(frames, streams), dim3(64), lds, s, window,
+                           heads, state_begin, state_phonemes, stay, final_, out_begin, targets, out_weights, held, row,
+                           rows, kept, cap, post, occupancy, state_stride, count);
+    return posterior_stream_launched(what);
+}
+
+int ppg_posterior_stream_flush(int device, void* state, int streams, int window, int graphs, int n_states, int n_arcs,
+                               int max_states, const int32_t* state_begin, const int32_t* state_phonemes,
+                               const float* stay, const float* initial, const float* final_, const int32_t* arc_begin,
+                               const int32_t* sources, const float* weights, const int32_t* out_begin,
+                               const int32_t* targets, const float* out_weights, const int32_t* which, int cap,
+                               float* post, float* occupancy, int state_stride, int32_t* begin, int32_t* count,
+                               double* total, void* stream) {
+    const char* what = "posterior_stream_flush";
+    if (const int rc = check_posterior_stream_state(what, state, streams, window, max_states)) return rc;
+    if (const int rc = check_posterior_stream_graphs(what, streams, graphs, n_states, n_arcs, max_states, sources,
+                                                     weights, targets, out_weights))
+        return rc;
+    if (const int rc = check_words(what, {state_begin, state_phonemes, stay, initial, final_, arc_begin, out_begin, post,
+                                          begin, count},
+                                   {sources, weights, targets, out_weights, which, occupancy}))
+        return rc;
+    if (const int rc = check_posterior_stream_outputs(what, cap, occupancy, state_stride, max_states, total)) return rc;
+    if (hipSetDevice(device) != hipSuccess)
+        return ppg::fail_message(PPG_EDEVICE, "no HIP device: the post-ops have no CPU path");
+    if (const int rc = allow_posterior_stream_lds<true>(what)) return rc;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const PosteriorStreamLayout w = posterior_stream_layout(streams, window, max_states);
+    char* st = static_cast<char*>(state);
+    PosteriorHead* heads = reinterpret_cast<PosteriorHead*>(st + w.heads);
+    const float* rows = reinterpret_cast<const float*>(st + w.rows);
+    const float4* kept = reinterpret_cast<const float4*>(st + w.kept);
+    const int row = posterior_row(max_states);
+    const int held = n_arcs < PHELD ? n_arcs : PHELD;
+    const size_t lds = (size_t)held * sizeof(uint2);
+    hipLaunchKernelGGL(posterior_stream_total, dim3(streams), dim3(64), 0, s, window, which, heads, state_begin, final_,
+                       row, rows, begin, count, total);
+    hipLaunchKernelGGL((posterior_stream_backward<1, true>), dim3(1, streams), dim3(64), lds, s, window, heads,
+                       state_begin, state_phonemes, stay, final_, out_begin, targets, out_weights, held, row, rows, kept,
+                       cap, post, occupancy, state_stride, count);
+    if (row > 64)
+        hipLaunchKernelGGL((posterior_stream_backward<4, true>), dim3(1, streams), dim3(64), lds, s, window, heads,
+                           state_begin, state_phonemes, stay, final_, out_begin, targets, out_weights, held, row, rows,
+                           kept, cap, post, occupancy, state_stride, count);
+    hipLaunchKernelGGL(posterior_stream_reset<false>, dim3((streams + 63) / 64), dim3(64), 0, s, streams, which, 0,
+                       static_cast<const int*>(nullptr), 0, 0, heads);
+    return posterior_stream_launched(what);
+}
 
 size_t ppg_posterior_workspace_bytes(int items, int frames, int max_states) {
     return posterior_sizes_fine(items, frames, max_states) ? posterior_layout(items, frames, max_states).bytes : 0;

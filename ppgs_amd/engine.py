@@ -233,6 +233,30 @@ SYMBOLS = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_posterior_stream_emitted': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    'ppg_posterior_stream_block': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_int64]),
+    'ppg_posterior_stream_state_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_posterior_stream_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    'ppg_posterior_stream_open': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    'ppg_posterior_stream_reset': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_posterior_stream_push': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'ppg_posterior_stream_flush': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_metrics_state_bytes': (ctypes.c_size_t, []),
     'ppg_metrics_reset': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_metrics_update': (ctypes.c_int, [
@@ -1367,6 +1391,91 @@ def viterbi_stream_flush(state, streams, window, packed, cap, which=None, want_g
             begin.data_ptr(), end.data_ptr(), score.data_ptr(), gop.data_ptr() if want_gop else None,
             count.data_ptr(), total.data_ptr(), forced.data_ptr(), torch.cuda.current_stream().cuda_stream))
     return states, phonemes, begin, end, score, gop, count, total, forced
+
+
+POSTERIOR_STREAM_MAX_PUSH = 2 ** 26 - 1  # PPG_POSTERIOR_STREAM_MAX_PUSH: frames * streams of one push
+
+PackedOutGraphs = collections.namedtuple('PackedOutGraphs', PackedGraphs._fields + ('out_begin', 'targets', 'out_weights'))
+
+
+def _out_graph_arguments(packed):
+    """The graph arguments of the ppg_posterior_stream_* entries from a PackedOutGraphs of device tensors."""
+    return _graph_arguments(packed) + (
+        packed.out_begin.data_ptr(), packed.targets.data_ptr() if packed.arcs else None,
+        packed.out_weights.data_ptr() if packed.arcs else None)
+
+
+def posterior_stream_state(device, streams, window, packed, block, lag, which=None):
+    """The device block of a live posterior (ppg_posterior_stream_*), opened: `streams` streams with a ring of `window`
+    frames each over the graphs of `packed` (a PackedOutGraphs of contiguous int32 / fp32 tensors on `device`), stream i
+    on graph which[i] (a device int32 tensor; None: graph 0), blocks of `block` frames smoothed by `lag` more.  uint8;
+    its owner passes it to the calls below with the same numbers and the same `packed`."""
+    size = library().ppg_posterior_stream_state_bytes(streams, window, packed.max_states)
+    if size == 0:
+        raise ValueError(f'a live posterior takes 1 to {VITERBI_STREAM_MAX_STREAMS} streams, a window that is a '
+                         f'multiple of 64 from {VITERBI_STREAM_MIN_WINDOW} to {VITERBI_STREAM_MAX_WINDOW} and graphs of '
+                         f'1 to {VITERBI_MAX_STATES} states, got {streams}, {window} and {packed.max_states}')
+    state = torch.empty((size,), dtype=torch.uint8, device=device)
+    posterior_stream_open(state, streams, window, packed, block, lag, which)
+    return state
+
+
+def posterior_stream_open(state, streams, window, packed, block, lag, which=None):
+    """ppg_posterior_stream_open on the current stream: the device checks the graphs and every stream starts at frame
+    0."""
+    with torch.cuda.device(state.device):
+        _check(library().ppg_posterior_stream_open(
+            state.device.index, state.data_ptr(), streams, window, *_out_graph_arguments(packed),
+            which.data_ptr() if which is not None else None, block, lag, torch.cuda.current_stream().cuda_stream))
+
+
+def posterior_stream_reset(state, streams, window, max_states, which=None):
+    """ppg_posterior_stream_reset on the current stream: `which` is None (all) or a device int32 (streams,) of flags."""
+    with torch.cuda.device(state.device):
+        _check(library().ppg_posterior_stream_reset(
+            state.device.index, state.data_ptr(), streams, window, max_states,
+            which.data_ptr() if which is not None else None, torch.cuda.current_stream().cuda_stream))
+
+
+def _posterior_outputs(device, streams, cap, max_states, want_states):
+    post = torch.zeros((streams, 40, cap), dtype=torch.float32, device=device)
+    states = torch.zeros((streams, cap, max_states), dtype=torch.float32, device=device) if want_states else None
+    begin = torch.zeros((streams,), dtype=torch.int32, device=device)
+    count = torch.zeros((streams,), dtype=torch.int32, device=device)
+    float64 = torch.zeros((streams,), dtype=torch.float64, device=device)
+    return post, states, begin, count, float64
+
+
+def posterior_stream_push(state, window, ppg, lengths, packed, cap, workspace, want_states=False):
+    """ppg_posterior_stream_push on the current stream: ppg (streams, 40, frames) fp32 and lengths (streams,) int32,
+    contiguous on the state's device; `packed` the graphs the state was opened with; workspace a uint8 tensor there ->
+    post (streams, 40, cap) fp32, the occupancy (streams, cap, max_states) fp32 (None without want_states), begin and
+    count (streams,) int32 and evidence (streams,) float64.  Column j is frame begin + j; columns at or past count are
+    zero."""
+    device = state.device
+    streams, frames = ppg.shape[0], ppg.shape[2]
+    post, states, begin, count, evidence = _posterior_outputs(device, streams, cap, packed.max_states, want_states)
+    with torch.cuda.device(device):
+        _check(library().ppg_posterior_stream_push(
+            device.index, state.data_ptr(), streams, window, ppg.data_ptr(), frames, lengths.data_ptr(),
+            *_out_graph_arguments(packed), cap, post.data_ptr(), states.data_ptr() if want_states else None,
+            packed.max_states, begin.data_ptr(), count.data_ptr(), evidence.data_ptr(), workspace.data_ptr(),
+            workspace.numel(), torch.cuda.current_stream().cuda_stream))
+    return post, states, begin, count, evidence
+
+
+def posterior_stream_flush(state, streams, window, packed, cap, which=None, want_states=False):
+    """ppg_posterior_stream_flush on the current stream -> the outputs of posterior_stream_push with total (streams,)
+    float64 in the place of evidence."""
+    device = state.device
+    post, states, begin, count, total = _posterior_outputs(device, streams, cap, packed.max_states, want_states)
+    with torch.cuda.device(device):
+        _check(library().ppg_posterior_stream_flush(
+            device.index, state.data_ptr(), streams, window, *_out_graph_arguments(packed),
+            which.data_ptr() if which is not None else None, cap, post.data_ptr(),
+            states.data_ptr() if want_states else None, packed.max_states, begin.data_ptr(), count.data_ptr(),
+            total.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return post, states, begin, count, total
 
 
 METRICS_FIXED_POINT = 2.0 ** 32        # the real-valued accumulators of PpgMetricsState count units of 2^-32
