@@ -453,7 +453,10 @@ int ppg_grid_sample(int device, const float* ppg, int rows, int frames,
  * ppg_dtw:
  *   ppg_x, ppg_y : device fp32 (pairs, 40, frames_x) and (pairs, 40, frames_y), padded to the longest item; pair b
  *                  compares item b of each side; frames past an item's length are never read
- *   lengths_x/_y : device int32[pairs], each in [1, frames_x] / [1, frames_y]
+ *   lengths_x/_y : device int32[pairs], each in [1, frames_x] / [1, frames_y].  They are read on the device, so the call
+ *                  cannot refuse a wrong one: a pair with a length of 0 or below gets total NaN, steps 0 and
+ *                  path_length 0, and its rows of path and path_cost are left alone; a length above frames_x /
+ *                  frames_y counts as frames_x / frames_y.  The other pairs of the call are not affected.
  *   mix          : device fp32 (40, 40) as ppg_distance's, or NULL
  *   total, steps : device fp32[pairs], int32[pairs]
  *   path         : NULL (distance only: no direction table, no trace-back), or device int32

@@ -1,4 +1,5 @@
-"""CPU restatement of ppgs_amd.dtw for the tests (tests/test_dtw_host.py, tests/test_gpu_dtw.py): the cost matrix
+"""CPU restatement of ppgs_amd.dtw for the tests (tests/test_dtw_host.py, tests/test_gpu_dtw.py; tests/dtw_probe.py
+restates the programme in fp32 and is held against this one): the cost matrix
 from the oracle's per-frame distance, a float64 dynamic programme with the documented tie-break (diagonal, then
 (i-1, j), then (i, j-1)) vectorised over anti-diagonals, and its own trace-back."""
 import numpy as np
