@@ -481,6 +481,62 @@ int ppg_dtw(int device, const float* ppg_x, int frames_x, const float* ppg_y, in
             void* stream);
 
 /*
+ * Weighted edit distance of two phoneme sequences, with the alignment as edit operations: the phoneme error rate of a
+ * recogniser's output against a transcript without times (no counterpart in the reference).
+ *
+ *   r[0 .. N-1], h[0 .. M-1]: reference and hypothesis tokens in [0, 40), 0 <= N, M <= PPG_EDIT_MAX_TOKENS.
+ *   D[0, 0] = 0 over (N + 1) x (M + 1) cells in fp32; every other cell takes, in this order of preference,
+ *     the diagonal   D[i-1, j-1] + sub[r[i-1], h[j-1]],
+ *     the deletion   D[i-1, j]   + del[r[i-1]],
+ *     the insertion  D[i, j-1]   + ins[h[j-1]],
+ *   each one fp32 add, a candidate outside the table not existing, and a later candidate replacing an earlier one
+ *   only if it is strictly smaller (comparisons only).  Row 0 and column 0 are therefore the sequential sums of ins
+ *   and del.  total = D[N, M].  The path is read back from (N, M) by the chosen candidates.
+ *
+ * ppg_edit_distance:
+ *   ref, hyp     : device int32 (pairs, tokens_ref) and (pairs, tokens_hyp), padded to the longest sequence; tokens
+ *                  past a pair's length are never read.  A width may be 0, and its pointer then NULL.
+ *   lengths_ref/_hyp : device int32[pairs], in [0, tokens_ref] / [0, tokens_hyp].  They are read on the device, so the
+ *                  call cannot refuse a wrong one: a length above the width counts as the width; a pair with a negative
+ *                  length, or with a token outside [0, 40) inside its lengths, is invalid: total NaN, counts and
+ *                  ops_length 0, its rows of ops left alone, and nothing added to the statistics but one count of
+ *                  invalid pairs.  The other pairs of the call are not affected.
+ *   sub, del, ins: device fp32 (40, 40), (40), (40), finite and >= 0, all three or all NULL; NULL is the unit costs
+ *                  sub = 1 - I, del = ins = 1, under which every value is a small integer, exact in fp32
+ *   total        : device fp32[pairs]
+ *   counts       : device int32 (pairs, 4): hits, substitutions, deletions, insertions of the path.  A diagonal step
+ *                  is a hit if the two tokens are equal and a substitution if not, whatever sub says.
+ *                  H + S + D = N, H + S + I = M; under the unit costs total = S + D + I.
+ *   ops          : NULL (no direction table, no trace-back), or device int32 (pairs, tokens_ref + tokens_hyp, 3):
+ *                  rows 0 .. K-1 of pair b, K = H + S + D + I, are its operations (kind, i, j) in forward order, kind
+ *                  0 hit / 1 substitution of r[i] by h[j], 2 deletion of r[i] (j = -1), 3 insertion of h[j] (i = -1);
+ *                  the rest is left alone
+ *   ops_length   : device int32[pairs] = K, required with ops (and NULL without)
+ *   statistics   : NULL, or (needs ops) a device accumulator of PPG_EDIT_STATISTICS int64 that the call ADDS to and
+ *                  never zeroes: a (41, 41) table -- [p, q] reference p matched to hypothesis q (hits on the diagonal),
+ *                  [p, 40] deletions of p, [40, q] insertions of q, [40, 40] unused -- then the number of valid pairs
+ *                  and the number of invalid pairs.  Integer sums: the result does not depend on the order or the
+ *                  grouping of the pairs.
+ *   workspace    : device memory, 16-byte aligned, at least ppg_edit_workspace_bytes(pairs, tokens_ref, tokens_hyp,
+ *                  ops != NULL) bytes: 4 B per pair and, with ops, one direction byte per cell (rows rounded up to 256,
+ *                  columns + 64).  It need not be initialised.
+ * Kernel launches on `stream` only: no allocation, synchronisation or copy.  Calls with workspaces of their own may
+ * run concurrently on several streams.
+ * PPG_EINVAL, with nothing launched and nothing written: a NULL required pointer, pairs <= 0, a negative width,
+ * PPG_EDIT_MAX_TOKENS or PPG_EDIT_MAX_PAIRS exceeded, some but not all of sub / del / ins, a short or unaligned
+ * workspace, ops without ops_length or the reverse, statistics without ops.  PPG_EDEVICE without a GPU.
+ * ppg_edit_workspace_bytes is host-only and returns 0 for arguments the call would refuse.
+ */
+#define PPG_EDIT_MAX_TOKENS 4096
+#define PPG_EDIT_MAX_PAIRS 65535
+#define PPG_EDIT_STATISTICS (41 * 41 + 2)
+size_t ppg_edit_workspace_bytes(int pairs, int tokens_ref, int tokens_hyp, int want_ops);
+int ppg_edit_distance(int device, const int32_t* ref, int tokens_ref, const int32_t* hyp, int tokens_hyp, int pairs,
+                      const int32_t* lengths_ref, const int32_t* lengths_hyp, const float* sub, const float* del,
+                      const float* ins, float* total, int32_t* counts, int32_t* ops, int32_t* ops_length,
+                      int64_t* statistics, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Forced alignment of a PPG to the phoneme sequence the speaker was meant to say, with goodness-of-pronunciation
  * scores, and the free-running counterpart (no counterpart in the reference, which takes phoneme timings from
  * outside aligners; its only use of a PPG as a sequence is the argmax + unique_consecutive decode of

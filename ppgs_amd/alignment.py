@@ -196,6 +196,7 @@ VITERBI_MAX_STATES = engine.VITERBI_MAX_STATES
 VITERBI_MAX_ARCS = engine.VITERBI_MAX_ARCS
 VITERBI_MAX_DEGREE = engine.VITERBI_MAX_DEGREE
 POSTERIOR_MAX_FRAMES = engine.POSTERIOR_MAX_FRAMES
+EDIT_MAX_TOKENS = engine.EDIT_MAX_TOKENS
 
 Alignment = collections.namedtuple('Alignment', ['phonemes', 'starts', 'total', 'score', 'gop'])
 Decoding = collections.namedtuple('Decoding', ['phonemes', 'starts'])
@@ -206,6 +207,7 @@ Hits = collections.namedtuple('Hits', ['phonemes', 'begin', 'end', 'total', 'mea
 Runs = collections.namedtuple('Runs', ['phonemes', 'begin', 'end', 'score', 'gop', 'count', 'total', 'forced'])
 Posterior = collections.namedtuple('Posterior', ['total', 'phonemes', 'states'])
 StateRuns = collections.namedtuple('StateRuns', ('states',) + Runs._fields)
+EditDistance = collections.namedtuple('EditDistance', ['total', 'hits', 'substitutions', 'deletions', 'insertions', 'ops'])
 PosteriorFrames = collections.namedtuple('PosteriorFrames', ['phonemes', 'states', 'begin', 'count', 'evidence', 'total'])
 
 
@@ -1772,3 +1774,132 @@ def frame_labels(starts, phonemes, frames):
     inner = starts[1:-1].to(torch.int64).contiguous()           # the N - 1 boundaries inside the utterance
     time = torch.arange(frames, dtype=torch.int64, device=starts.device)
     return phonemes.to(starts.device)[torch.bucketize(time, inner, right=True)]
+
+
+def edit_costs(sub=None, delete=None, insert=None):
+    """The costs of `edit_distance` as checked CPU tensors (sub (40, 40), delete (40,), insert (40,)), fp32, finite
+    and >= 0; one left out is its unit default (1 - I, ones).  None if all three are left out.  Host only."""
+    if sub is None and delete is None and insert is None:
+        return None
+    count = len(PHONEMES)
+    defaults = (1. - torch.eye(count), torch.ones(count), torch.ones(count))
+    out = []
+    for value, default, name in zip((sub, delete, insert), defaults, ('sub', 'delete', 'insert')):
+        if value is None:
+            value = default
+        if not torch.is_tensor(value) or tuple(value.shape) != tuple(default.shape) or not value.is_floating_point():
+            raise ValueError(f'{name} must be a floating-point tensor of shape {tuple(default.shape)}')
+        value = value.detach().to(device='cpu', dtype=torch.float32).contiguous()
+        if not bool(torch.isfinite(value).all()) or bool((value < 0).any()):
+            raise ValueError(f'{name} must be finite and >= 0')
+        out.append(value)
+    return tuple(out)
+
+
+def _ignored(ignore):
+    """`ignore` as a sorted list of phoneme indices."""
+    if ignore is None:
+        return []
+    if isinstance(ignore, (str, int)) and not isinstance(ignore, bool):
+        ignore = [ignore]
+    return sorted(set(_sequence(list(ignore))))
+
+
+def _edit_rows(sequences, what, ignore):
+    """The host checks of one side of an edit-distance call: every sequence as a list of checked indices with the
+    ignored ones dropped, or, for a device tensor, as it is (shape and type checked here, its values by the kernel)."""
+    rows = []
+    for sequence in sequences:
+        if torch.is_tensor(sequence) and sequence.is_cuda:
+            if sequence.dim() != 1 or sequence.is_floating_point() or sequence.is_complex() or \
+                    sequence.dtype == torch.bool:
+                raise ValueError(f'a phoneme sequence must be a one-dimensional integer tensor, got '
+                                 f'{tuple(sequence.shape)} {sequence.dtype}')
+            rows.append(sequence)
+        else:
+            rows.append([value for value in _sequence(sequence) if value not in ignore])
+        if len(rows[-1]) > EDIT_MAX_TOKENS:
+            raise ValueError(f'{what}: edit distance takes at most {EDIT_MAX_TOKENS} phonemes per sequence, got '
+                             f'{len(rows[-1])}')
+    return rows
+
+
+def _edit_table(rows, ignore, device):
+    """The rows of _edit_rows as (a padded int32 table on the device, its lengths as an int32 device tensor).
+    Nothing here waits for the device."""
+    width = max(1, max(len(row) for row in rows))
+    host = torch.zeros((len(rows), width), dtype=torch.int32)
+    for index, row in enumerate(rows):
+        if isinstance(row, list) and row:
+            host[index, :len(row)] = torch.tensor(row, dtype=torch.int32)
+    table = host.to(device)
+    lengths = torch.tensor([len(row) for row in rows], dtype=torch.int32).to(device)
+    on_device = [index for index, row in enumerate(rows) if not isinstance(row, list)]
+    for index in on_device:
+        row = rows[index].to(device=device, dtype=torch.int64)
+        # an index that would not survive the narrowing to int32 stays invalid for the kernel to find
+        row = torch.where((row < 0) | (row >= len(PHONEMES)), torch.full_like(row, -1), row)
+        table[index, :len(row)] = row.to(torch.int32)
+    if ignore and on_device:
+        # drop the ignored phonemes of the device rows in order, without learning how many there were
+        keep = torch.arange(width, device=device)[None] < lengths[:, None]
+        for index in ignore:
+            keep &= table != index
+        target = torch.where(keep, torch.cumsum(keep, 1) - 1, torch.full((1, 1), width, device=device))
+        packed = torch.zeros((len(rows), width + 1), dtype=torch.int32, device=device)
+        packed.scatter_(1, target, table)
+        table, lengths = packed[:, :width].contiguous(), keep.sum(1).to(torch.int32)
+    return table, lengths
+
+
+def _edit_sides(reference, hypothesis):
+    """(batched, references, hypotheses).  A pair is two sequences; a batch is two lists (or tuples) of as many
+    sequences.  A side counts as a batch if it is a non-empty list holding at least one list, tuple or tensor of one
+    or more dimensions; the call is a batch if either side is one, and then both must be.  An empty list is therefore
+    always an empty sequence: two empty lists are one pair of empty sequences, never a batch of none."""
+    def is_batch(value):
+        return isinstance(value, (list, tuple)) and any(
+            isinstance(v, (list, tuple)) or (torch.is_tensor(v) and v.dim() > 0) for v in value)
+    if not (is_batch(reference) or is_batch(hypothesis)):
+        return False, [reference], [hypothesis]
+    if not (is_batch(reference) and is_batch(hypothesis)) or len(reference) != len(hypothesis):
+        raise ValueError('a batch is two lists of as many sequences')
+    return True, list(reference), list(hypothesis)
+
+
+def edit_distance(reference, hypothesis, sub=None, delete=None, insert=None, ignore=None, ops=False):
+    """The weighted edit distance of phoneme sequences and the alignment behind it -- what a phoneme error rate and a
+    list of mispronunciations are made of (ppg_edit_distance).
+
+    One pair: two sequences of phoneme names or indices, or one-dimensional integer tensors on the CPU or the device
+    (`Decoding.phonemes`, `Recognition.phonemes`, a transcript); either may be empty.  A batch: two lists of as many
+    such sequences.  A list that holds a list, a tuple or a tensor of one or more dimensions is a batch; an empty
+    list is an empty sequence, so two empty lists are one pair of empty sequences and a batch has at least one pair.  `sub` (40, 40), `delete` (40,) and `insert` (40,) are finite costs >= 0 indexed by reference and
+    hypothesis phoneme; the defaults are the unit costs 1 - I and ones.  `ignore` names phonemes (e.g. '<silent>')
+    that are dropped from both sides first.
+
+    Over the fp32 table D[0, 0] = 0 a cell prefers the diagonal D[i-1, j-1] + sub, then the deletion D[i-1, j] +
+    delete, then the insertion D[i, j-1] + insert, a later one winning only if strictly smaller; the path is read back
+    from the last cell.  Returns EditDistance(total, hits, substitutions, deletions, insertions, ops): device tensors,
+    0-d for a pair and (B,) for a batch (total fp32, the counts int32); a diagonal step is a hit if the two phonemes
+    are equal and a substitution otherwise.  With `ops`, a (K, 3) int32 device tensor per pair of (kind, i, j) in
+    forward order: 0 hit, 1 substitution, 2 deletion of reference[i] (j = -1), 3 insertion of hypothesis[j] (i = -1);
+    indices count the phonemes left after `ignore`.  A device sequence with an index outside [0, 40) gives total NaN
+    and zero counts.  Batch results equal the single calls bit for bit."""
+    batched, references, hypotheses = _edit_sides(reference, hypothesis)
+    costs = edit_costs(sub, delete, insert)
+    ignore = _ignored(ignore)
+    rows = [_edit_rows(references, 'reference', ignore), _edit_rows(hypotheses, 'hypothesis', ignore)]
+    device = core.device_for(None, next((row for row in rows[0] + rows[1] if torch.is_tensor(row)), None))
+    ref, lengths_ref = _edit_table(rows[0], ignore, device)
+    hyp, lengths_hyp = _edit_table(rows[1], ignore, device)
+    if costs is not None:
+        costs = [c.to(device) for c in costs]
+    total, counts, table, count = engine.edit_pairs(ref, hyp, lengths_ref, lengths_hyp, costs, want_ops=ops)
+    out_ops = None
+    if ops:
+        out_ops = [table[b, :k] for b, k in enumerate(count.tolist())]
+    if not batched:
+        return EditDistance(total[0], counts[0, 0], counts[0, 1], counts[0, 2], counts[0, 3],
+                            out_ops[0] if ops else None)
+    return EditDistance(total, counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], out_ops)

@@ -150,6 +150,11 @@ SYMBOLS = {
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'ppg_edit_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_edit_distance': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'ppg_align_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'ppg_align': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
@@ -800,6 +805,85 @@ def dtw_pairs(ppg_x, ppg_y, lengths_x, lengths_y, mix=None, want_path=False, wan
                 cost[at:].data_ptr() if want_cost else None,
                 workspace.data_ptr(), size, stream))
     return total, steps, path, cost
+
+
+EDIT_MAX_TOKENS = 4096          # PPG_EDIT_MAX_TOKENS
+EDIT_MAX_PAIRS = 65535          # PPG_EDIT_MAX_PAIRS, per call of the library
+EDIT_STATISTICS = 41 * 41 + 2   # PPG_EDIT_STATISTICS: the (41, 41) table, then the valid and the invalid pairs
+EDIT_WORKSPACE_BYTES = 1 << 30  # a larger batch runs as several calls, each within this much workspace
+
+
+def edit_pairs(ref, hyp, lengths_ref, lengths_hyp, costs=None, want_ops=False, statistics=None):
+    """Weighted edit distance of pair b = (ref[b, :lengths_ref[b]], hyp[b, :lengths_hyp[b]]) (ppg_edit_distance):
+    padded int32 (pairs, tokens_ref) and (pairs, tokens_hyp) on a GPU; lengths as host integers or as int32 device
+    tensors; `costs` None for the unit costs or device fp32 (sub (40, 40), del (40,), ins (40,)) -> total (pairs,) fp32,
+    counts (pairs, 4) int32 = hits, substitutions, deletions, insertions, and with want_ops the padded operations
+    (pairs, tokens_ref + tokens_hyp, 3) int32 and their number K (pairs,) int32, else None.  `statistics`, an int64
+    device tensor of EDIT_STATISTICS words, is added to; without want_ops the operations it is made from live in a
+    buffer of one group of pairs and only K is returned.  With want_ops the padded operations of the WHOLE batch are
+    an output, 12 (tokens_ref + tokens_hyp) bytes per pair outside the workspace cap.  Nothing here waits for the
+    device."""
+    if not (torch.is_tensor(ref) and torch.is_tensor(hyp) and ref.is_cuda and hyp.is_cuda):
+        raise PpgError('ppgs_amd: the post-ops work on HIP device tensors')
+    if ref.dim() != 2 or hyp.dim() != 2 or ref.shape[0] != hyp.shape[0] or ref.shape[0] < 1 or \
+            ref.dtype != torch.int32 or hyp.dtype != torch.int32:
+        raise ValueError(f'token tables must be int32 (pairs >= 1, tokens), got {tuple(ref.shape)} {ref.dtype} and '
+                         f'{tuple(hyp.shape)} {hyp.dtype}')
+    pairs, tokens_ref, tokens_hyp = ref.shape[0], ref.shape[1], hyp.shape[1]
+    if tokens_ref > EDIT_MAX_TOKENS or tokens_hyp > EDIT_MAX_TOKENS:
+        raise ValueError(f'edit distance takes at most {EDIT_MAX_TOKENS} tokens per side, got {tokens_ref} and '
+                         f'{tokens_hyp}')
+    device = ref.device
+    keep_ops = bool(want_ops)
+    want_ops = keep_ops or statistics is not None
+    if statistics is not None and not (
+            torch.is_tensor(statistics) and statistics.device == device and statistics.dtype == torch.int64 and
+            statistics.is_contiguous() and statistics.numel() == EDIT_STATISTICS):
+        raise ValueError(f'statistics must be a contiguous int64 tensor of {EDIT_STATISTICS} words on {device}')
+    if costs is not None:
+        shapes = ((40, 40), (40,), (40,))
+        if len(costs) != 3 or any(
+                not torch.is_tensor(c) or c.device != device or c.dtype != torch.float32 or tuple(c.shape) != shape
+                for c, shape in zip(costs, shapes)):
+            raise ValueError(f'costs must be fp32 (40, 40), (40,), (40,) on {device}')
+        costs = [c.contiguous() for c in costs]
+    ref, hyp = ref.contiguous(), hyp.contiguous()
+    lengths = []
+    for value in (lengths_ref, lengths_hyp):
+        if torch.is_tensor(value) and value.is_cuda:
+            value = value.to(device=device, dtype=torch.int32).contiguous()
+        else:
+            value = torch.tensor([int(v) for v in value], dtype=torch.int32).to(device)
+        if value.shape != (pairs,):
+            raise ValueError(f'{value.numel()} lengths for {pairs} pairs')
+        lengths.append(value)
+    total = torch.empty((pairs,), dtype=torch.float32, device=device)
+    counts = torch.empty((pairs, 4), dtype=torch.int32, device=device)
+    ops_length = torch.empty((pairs,), dtype=torch.int32, device=device) if want_ops else None
+    lib = library()
+    per_pair = lib.ppg_edit_workspace_bytes(1, tokens_ref, tokens_hyp, int(want_ops))
+    group = max(1, min(pairs, EDIT_MAX_PAIRS, EDIT_WORKSPACE_BYTES // per_pair))
+    ops = None
+    if keep_ops:
+        ops = torch.zeros((pairs, tokens_ref + tokens_hyp, 3), dtype=torch.int32, device=device)
+    elif want_ops:      # for the statistics only: one group's worth, written over by every call on this stream
+        ops = torch.empty((group, tokens_ref + tokens_hyp, 3), dtype=torch.int32, device=device)
+    size = lib.ppg_edit_workspace_bytes(group, tokens_ref, tokens_hyp, int(want_ops))
+    workspace = torch.empty((size,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for at in range(0, pairs, group):
+            count = min(group, pairs - at)
+            _check(lib.ppg_edit_distance(
+                device.index, ref[at:].data_ptr() if tokens_ref else None, tokens_ref,
+                hyp[at:].data_ptr() if tokens_hyp else None, tokens_hyp, count,
+                lengths[0][at:].data_ptr(), lengths[1][at:].data_ptr(),
+                costs[0].data_ptr() if costs else None, costs[1].data_ptr() if costs else None,
+                costs[2].data_ptr() if costs else None, total[at:].data_ptr(), counts[at:].data_ptr(),
+                (ops[at:] if keep_ops else ops).data_ptr() if want_ops else None,
+                ops_length[at:].data_ptr() if want_ops else None,
+                statistics.data_ptr() if statistics is not None else None, workspace.data_ptr(), size, stream))
+    return total, counts, ops if keep_ops else None, ops_length
 
 
 ALIGN_MAX_FRAMES = 4096          # PPG_ALIGN_MAX_FRAMES
