@@ -877,6 +877,56 @@ int ppg_search(int device, const float* ppg, int frames, int items, const int32_
                int32_t* curve_begin, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Phrase search over a phoneme graph: ppg_search with a graph of ppg_viterbi in the place of the one chain, so that one
+ * query holds pronunciation variants, pauses a speaker may or may not make between words, and consonants that may be
+ * dropped.  Not in the reference.
+ *
+ * One pair is a recording P (40, T) and a graph as ppg_viterbi takes it: S states, sym, stay, ordered in-arcs
+ * (src[j], w[j]), initial, final, every weight finite or -inf.  The prepared frame is ppg_align's and the emission is
+ * ppg_search's: r[t, n] = logp[t][sym[n]] - m[t], one fp32 subtraction.  Every state carries D (fp32) and a begin b;
+ * before frame 0 every D is -inf.  For every t >= 0, frame 0 included:
+ *   best = D[t-1, n] + stay[n]; bb = b[t-1, n]
+ *   for j in list order: c = D[t-1, src[j]] + w[j]; if c > best: best = c, bb = b[t-1, src[j]]
+ *   if initial[n] > best: best = initial[n], bb = t          (a fresh start comes last and only if strictly better)
+ *   D[t, n] = r[t, n] + best; b[t, n] = bb
+ * Comparisons only, strict >; one fp32 addition per candidate, in order of t; -inf + finite = -inf and -inf > -inf is
+ * false, so an unreached state never makes a NaN.  curve_total[t] is the largest D[t, n] + final[n], the lowest n on
+ * ties; curve_begin[t] is that state's b, and -1 where the total is -inf.  Hits, top, threshold, mean (one fp32
+ * division), the tie to the later end frame, the sentinels past count and count itself are ppg_search's.  Under a chain
+ * (state n takes one arc from n - 1, every weight 0, initial 0 on state 0 and final 0 on state N - 1, -inf elsewhere)
+ * the curve and the hits are ppg_search's bit for bit.  The states inside a hit (begin, end) are the best path of
+ * ppg_viterbi through the same graph on frames begin .. end - 1: the two emissions differ by m[t], which no path through
+ * a fixed span can change.
+ *
+ * ppg_search_graph: every graph is searched in every recording (there is no `which`).
+ *   ppg, frames, items, lengths : as ppg_search
+ *   graphs .. weights : the packed graphs and their host integers exactly as ppg_viterbi takes them; max_states is
+ *                     1 .. PPG_VITERBI_MAX_STATES and bounds every graph of the call
+ *   top, threshold, begin, end, total, mean, count, curve_total, curve_begin : as ppg_search, with `graphs` in the place
+ *                     of `queries`: (items, graphs, top), (items, graphs) and (items, graphs, frames)
+ *   workspace       : device memory, 16-byte aligned, at least ppg_search_graph_workspace_bytes(items, frames, graphs):
+ *                     the prepared frames once per recording (176 bytes a frame), every pair's curve totals, every
+ *                     pair's curve begins, a verdict word per graph and a word per graph that holds 1, each block
+ *                     256-byte aligned.  Need not be initialised: the call reads nothing it has not written.
+ * The device checks the graphs as ppg_viterbi does.  A pair whose graph was refused, or has more than
+ * PPG_SEARCH_GRAPH_MAX_STATES states or PPG_SEARCH_GRAPH_MAX_ARCS arcs, or whose length is outside [1, frames], has
+ * count = -1 and nothing else of it is written.
+ * PPG_EINVAL, and nothing launched, for what ppg_search and ppg_viterbi refuse on the host: NULL or unaligned pointers,
+ * a short workspace, a limit exceeded (PPG_SEARCH_MAX_FRAMES, PPG_SEARCH_MAX_ITEMS, PPG_SEARCH_MAX_QUERIES graphs,
+ * PPG_VITERBI_MAX_STATES), a NaN threshold, top outside 1 .. PPG_SEARCH_MAX_HITS, one curve pointer without the other,
+ * n_states or n_arcs that cannot be.  ppg_search_graph_workspace_bytes is host-only and returns 0 for such sizes.
+ */
+#define PPG_SEARCH_GRAPH_MAX_STATES 256      /* D and b of every state twice over are 4 KiB of LDS */
+#define PPG_SEARCH_GRAPH_MAX_ARCS   4096     /* per graph: 32 KiB of LDS hold them all */
+size_t ppg_search_graph_workspace_bytes(int items, int frames, int graphs);
+int ppg_search_graph(int device, const float* ppg, int frames, int items, const int32_t* lengths, int graphs,
+                     int n_states, int n_arcs, int max_states, const int32_t* state_begin,
+                     const int32_t* state_phonemes, const float* stay, const float* initial, const float* final_,
+                     const int32_t* arc_begin, const int32_t* sources, const float* weights, int top, float threshold,
+                     int32_t* begin, int32_t* end, float* total, float* mean, int32_t* count, float* curve_total,
+                     int32_t* curve_begin, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Live phrase search: ppg_search carried across the pushes of a stream (keyword spotting on a live PPG, e.g. the
  * frames an audio stream emits).  A push does work proportional to its own frames, whatever the age of the stream.
  * Not in the reference.

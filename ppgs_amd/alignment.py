@@ -130,6 +130,28 @@ mean); hits are disjoint and listed in the order taken.  Entries past `count` ar
     b, e = int(hits.begin[0]), int(hits.end[0])
     inside = ppgs_amd.alignment.forced(ppg[:, b:e], ['hh', 'ah', 'l', 'ow'])     # the phoneme boundaries inside a hit
 
+Phrase search over a graph (`search_graph`, ppg_search_graph): a real keyword is not one chain.  "either" has two
+pronunciations, a phrase of several words may or may not have a pause between them, and a final consonant may be
+dropped.  `search_graph` takes a Graph of at most 256 states and 4096 arcs as the query, with a free start and a free
+end.  Every state carries D and a begin b; before frame 0 every D is -inf, and for every t >= 0:
+
+    r[t, n] = logp[t][sym[n]] - max_q logp[t][q]                       the emission of `search`
+    best = D[t-1, n] + stay[n], bb = b[t-1, n]
+    for j in list order:  c = D[t-1, src[j]] + w[j];  if c > best: best = c, bb = b[t-1, src[j]]
+    if initial[n] > best: best = initial[n], bb = t                    a fresh start: last, and only if strictly better
+    D[t, n] = r[t, n] + best;  b[t, n] = bb                            fp32, one addition per candidate, in order of t
+
+curve_total[t] is the largest D[t, n] + final[n] (the lowest n on ties), curve_begin[t] that state's b, -1 where the
+total is -inf; the hits are picked as `search` picks them.  `search_graph(ppg, chain_graph(s))` is `search(ppg, s)` bit
+for bit.  The path and the variants inside a hit are `viterbi(ppg[:, b:e], graph)`: the two emissions differ by the
+frame's maximum, which no path through a fixed span can change.
+
+    graph, word_of, variant_of = ppgs_amd.alignment.phrase_graph([[['iy', 'dh', 'er'], ['ay', 'dh', 'er']], [['w', 'ey']]])
+    hits = ppgs_amd.alignment.search_graph(ppg, graph, top=5, threshold=-1.)
+    b, e = int(hits.begin[0]), int(hits.end[0])
+    said = [variant_of[n] for n in ppgs_amd.alignment.viterbi(ppg[:, b:e], graph).states.tolist()]
+Not here: a live form, graphs over 256 states (a word loop belongs to `viterbi`).
+
 Live phrase search (`SearchStream`, ppg_search_stream_*): the same curve carried across the pushes of a stream, bit for
 bit whatever the push sizes, with an online rule that gives a hit out once nothing later can overlap and beat it.
 
@@ -191,6 +213,9 @@ RECOGNIZE_MAX_FRAMES = engine.RECOGNIZE_MAX_FRAMES
 SEARCH_MAX_FRAMES = engine.SEARCH_MAX_FRAMES
 SEARCH_MAX_PHONEMES = engine.SEARCH_MAX_PHONEMES
 SEARCH_MAX_HITS = engine.SEARCH_MAX_HITS
+SEARCH_GRAPH_MAX_STATES = engine.SEARCH_GRAPH_MAX_STATES
+SEARCH_GRAPH_MAX_ARCS = engine.SEARCH_GRAPH_MAX_ARCS
+SEARCH_GRAPH_MAX_GRAPHS = engine.SEARCH_GRAPH_MAX_GRAPHS
 VITERBI_MAX_FRAMES = engine.VITERBI_MAX_FRAMES
 VITERBI_MAX_STATES = engine.VITERBI_MAX_STATES
 VITERBI_MAX_ARCS = engine.VITERBI_MAX_ARCS
@@ -204,6 +229,7 @@ Recognition = collections.namedtuple('Recognition', Alignment._fields)
 Graph = collections.namedtuple('Graph', ['phonemes', 'stay', 'offsets', 'sources', 'weights', 'initial', 'final'])
 Path = collections.namedtuple('Path', ['states', 'phonemes', 'starts', 'total', 'score', 'gop'])
 Hits = collections.namedtuple('Hits', ['phonemes', 'begin', 'end', 'total', 'mean', 'count', 'curve'])
+GraphHits = collections.namedtuple('GraphHits', ['begin', 'end', 'total', 'mean', 'count', 'curve'])
 Runs = collections.namedtuple('Runs', ['phonemes', 'begin', 'end', 'score', 'gop', 'count', 'total', 'forced'])
 Posterior = collections.namedtuple('Posterior', ['total', 'phonemes', 'states'])
 StateRuns = collections.namedtuple('StateRuns', ('states',) + Runs._fields)
@@ -737,8 +763,22 @@ def pronunciations(words, silence=True):
     total `forced(..., optional=)` gives over all combinations of variants.  word_of[n] and variant_of[n] are the word
     and its variant state n belongs to, -1 for the silences: read the words' times and the variants chosen off
     `Path.states`.  Host only."""
+    return _word_graph(words, silence, silence, 'pronunciations')
+
+
+def phrase_graph(words, pauses=True):
+    """A phrase whose words have alternative pronunciations, for `search_graph`: (graph, word_of, variant_of).  It is
+    `pronunciations` without the silence before the first word and after the last, which a hit would otherwise
+    swallow: with `pauses` an optional '<silent>' state stands between words only, and `pauses=False` equals
+    `pronunciations(words, silence=False)` field for field.  The path begins in a first state of the first word and
+    ends in a last state of the last.  `search_graph` takes at most 256 states and 4096 arcs.  Host only."""
+    return _word_graph(words, bool(pauses), False, 'phrase_graph')
+
+
+def _word_graph(words, between, around, what):
+    """The graph of `pronunciations` and `phrase_graph`: an optional silence between words and around the transcript."""
     if isinstance(words, (str, bytes)) or not isinstance(words, (list, tuple)) or len(words) < 1:
-        raise ValueError('pronunciations takes a non-empty list of words, each a list of alternative phoneme sequences')
+        raise ValueError(f'{what} takes a non-empty list of words, each a list of alternative phoneme sequences')
     quiet = PHONEME_TO_INDEX_MAPPING['<silent>']
     symbols, into, word_of, variant_of = [], [], [], []
 
@@ -751,7 +791,7 @@ def pronunciations(words, silence=True):
     begins, ends = [], []                                      # where the path may begin; the last states so far
     for index, word in enumerate(words):
         before = list(ends)
-        if silence:
+        if around if index == 0 else between:
             before = [state(quiet, -1, -1, ends)] + before     # the pause first: advance before skip
         if index == 0:
             begins = list(before)
@@ -764,7 +804,7 @@ def pronunciations(words, silence=True):
                     begins.append(at)
                 sources = [at]
             ends.append(at)
-    if silence:
+    if around:
         ends = ends + [state(quiet, -1, -1, ends)]
     count = len(symbols)
     initial, final = [-math.inf] * count, [-math.inf] * count
@@ -1068,6 +1108,48 @@ def search(ppg, phonemes, lengths=None, top=1, threshold=None, curve=False):
     names = [table[q, :n] for q, n in enumerate(counts)]
     return Hits(names if several else names[0], drop(begin), drop(end), drop(total), drop(mean), drop(count),
                 None if curves is None else (drop(curves[0]), drop(curves[1])))
+
+
+def search_graph(ppg, graphs, lengths=None, top=1, threshold=None, curve=False):
+    """Find where a path through a Graph is said in `ppg`: GraphHits(begin, end, total, mean, count, curve).
+
+    `search` with a graph as the query (the module's text): `graphs` is one Graph (`phrase_graph`, `chain_graph`,
+    `graph`, `pronunciations`) of at most 256 states and 4096 arcs, or a list of Q of them; every graph is searched in
+    every recording.  `ppg`, `lengths`, `top`, `threshold`, `curve`, the shapes and the dropped axes are `search`'s: the
+    B axis is dropped for a single recording and the Q axis for a single graph.  A graph that no span fits has count 0.
+    `hit_segments` takes the result; the states inside hit h are `viterbi(ppg[:, begin[h]:end[h]], graph).states`.
+    Nothing here waits for the device."""
+    batched, batch, frames = _ppg(ppg, SEARCH_MAX_FRAMES, 'search_graph')
+    if not batched and lengths is not None:
+        raise ValueError('lengths go with a batch: slice a single PPG instead')
+    lengths = _lengths(lengths, batch, frames)
+    several = isinstance(graphs, (list, tuple)) and not isinstance(graphs, Graph)
+    values = list(graphs) if several else [graphs]
+    if not 1 <= len(values) <= SEARCH_GRAPH_MAX_GRAPHS:
+        raise ValueError(f'search_graph takes 1 to {SEARCH_GRAPH_MAX_GRAPHS} graphs, got {len(values)}')
+    packed = [_checked_graph(value) for value in values]
+    for index, value in enumerate(packed):
+        count, arcs = value.phonemes.shape[0], value.sources.shape[0]
+        if count > SEARCH_GRAPH_MAX_STATES or arcs > SEARCH_GRAPH_MAX_ARCS:
+            raise ValueError(f'search_graph takes graphs of at most {SEARCH_GRAPH_MAX_STATES} states and '
+                             f'{SEARCH_GRAPH_MAX_ARCS} arcs, graph {index} has {count} and {arcs}')
+    if isinstance(top, bool) or not isinstance(top, int) or not 1 <= top <= SEARCH_MAX_HITS:
+        raise ValueError(f'top must be an integer from 1 to {SEARCH_MAX_HITS}, got {top!r}')
+    threshold = -math.inf if threshold is None else float(threshold)
+    if math.isnan(threshold):
+        raise ValueError('the threshold is NaN')
+    counts, state_begin, arc_begin, joined = _joined_graphs(packed)
+    device = core.device_for(None, ppg)
+    x = ppg.to(device)
+    begin, end, total, mean, count, curves = engine.search_graph_items(
+        x if batched else x[None], lengths, state_begin, joined('phonemes'), joined('stay'), joined('initial'),
+        joined('final'), arc_begin, joined('sources'), joined('weights'), top, threshold, bool(curve), max(counts))
+
+    def drop(tensor):
+        tensor = tensor if several else tensor[:, 0]
+        return tensor if batched else tensor[0]
+    return GraphHits(drop(begin), drop(end), drop(total), drop(mean), drop(count),
+                     None if curves is None else (drop(curves[0]), drop(curves[1])))
 
 
 class SearchStream:

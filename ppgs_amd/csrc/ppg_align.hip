@@ -3,7 +3,9 @@
 // it the same search carried across the pushes of a stream (ppg_search_stream_*), then the phoneme
 // recogniser, the best path through all 40 phonemes under a transition model (ppg_recognize), and last
 // that recogniser carried across the pushes of a stream (ppg_recognize_stream_*).  The best path through a
-// graph of phoneme states (ppg_viterbi) follows the live recogniser.
+// graph of phoneme states (ppg_viterbi) follows the live recogniser.  The phrase search over such a graph
+// (ppg_search_graph) stands at the very end of the file, behind the host entries of all the others, with
+// its own host entries.
 //
 //   e[t, n] = logf(min(max(P[s[n], t], 1e-8), 1 - 1e-8))                      (the clamp of ppg_distance)
 //   D[0, 0] = e[0, 0];  D[0, n > 0] = -inf
@@ -3225,6 +3227,349 @@ int ppg_viterbi_stream_flush(int device, void* state, int streams, int window, i
                        reinterpret_cast<const uint8_t*>(st + w.back), reinterpret_cast<const float*>(st + w.kept),
                        reinterpret_cast<int*>(st + w.labels), cap, states, phonemes, begin, end, score, gop, count,
                        total, forced);
+    return launched(what);
+}
+
+}  // extern "C"
+
+// ---- phrase search over a phoneme graph (ppg_search_graph) ----
+//
+// ppg_search with a graph of ppg_viterbi in the place of the one chain: pronunciation variants, optional pauses between
+// words, a final consonant that may be dropped, all in one query.  One pair is a recording P (40, T) and a graph as in
+// ppg_viterbi: S states, sym, stay, ordered in-arcs (src[j], w[j]), initial, final, every weight finite or -inf.  The
+// prepared frame is align_prepare's, the emission is the search's: r[t, n] = logp[t][sym[n]] - m[t], one fp32
+// subtraction.  Every state carries D (fp32) and a begin b; before frame 0 every D is -inf.  For every t >= 0, frame 0
+// included:
+//   best = D[t-1, n] + stay[n]; bb = b[t-1, n]
+//   for j in list order: c = D[t-1, src[j]] + w[j]; if c > best: best = c, bb = b[t-1, src[j]]
+//   if initial[n] > best: best = initial[n], bb = t          a fresh start comes last and only if strictly better
+//   D[t, n] = r[t, n] + best; b[t, n] = bb
+// Comparisons only, strict >; one fp32 addition per candidate, in order of t; -inf + finite = -inf and -inf > -inf is
+// false, so an unreached state never makes a NaN.  Per end frame t, curve_total[t] is the largest D[t, n] + final[n],
+// the lowest n on ties (first_largest's rule), curve_begin[t] that state's b, and -1 where the total is -inf.  Hits,
+// top, threshold, mean, the tie to the later end frame, the sentinels and count are search_pick's: that kernel runs
+// unchanged on the curve with an array of ones for the queries' lengths (it uses a length only to skip the end frames
+// below N - 1, whose begin is -1 anyway).  Under chain_graph(s) all weights are 0 and D + 0 is exact; state 0 has the
+// candidates stay, then the fresh start, state n > 0 stay, then advance: the search's recurrence candidate for
+// candidate, so the curve and the hits are ppg_search's bit for bit.
+//   search_graph_programme  grid (graphs, items), one wave per pair, viterbi_programme's structure: D of frame t-1 is
+//                           read by index from a double buffer in LDS, a second double buffer holds the begins, the
+//                           arcs are copied to LDS once per pair, one barrier per frame, the prepared frames staged
+//                           CHUNK at a time with the next chunk in flight.  A graph has at most 256 states here, so a
+//                           frame is ONE pass (lane l takes state l if S <= 64, else the four states 4 l .. 4 l + 3)
+//                           and a lane's states never change: what viterbi_programme keeps of a state in LDS (the
+//                           table word, stay), initial, final and the state's first arcs themselves (four where a
+//                           lane has one state, two where it has four) stand in registers for the whole recording,
+//                           so D and b at those arcs' sources are read beside the state's own and a frame of a chain
+//                           or a phrase is one LDS round trip.  Of the arcs beyond only the SOURCE taken is tracked;
+//                           its begin is read once, after the last compare.  No back-pointers.  The curve: per frame
+//                           a lane leaves its own largest D + final and that state's b in LDS (a row per frame of
+//                           the chunk); after the chunk lane u takes frame u, walks the lanes that hold states in
+//                           ascending order with a strict compare (the lowest state of equal values) and the wave
+//                           writes the chunk's curve in two coalesced stores.  A 6-step __shfl_xor butterfly per
+//                           frame was built first and measured: 742 ns per frame for the chain of 8 against 312 with
+//                           the reduction left out; this form costs the same with one final state as
+//                           with two, so there is no shortcut for a single final state.
+// The legal graphs (256 states, 4096 arcs) always fit the held block, so there is no arcs-from-memory path.
+
+namespace {
+
+constexpr int GSTATES = PPG_SEARCH_GRAPH_MAX_STATES;
+static_assert(GSTATES == 256 && PPG_SEARCH_GRAPH_MAX_ARCS == VHELD, "one pass of four states a lane; every graph's arcs are held");
+
+struct SearchGraphLayout {
+    size_t logp, totals, begins, verdict, ones, bytes;         // byte offsets into the workspace
+};
+
+// (65535 x 65535 pairs of 262144 frames are 9.0e15 bytes: the limits keep this inside a size_t)
+inline SearchGraphLayout search_graph_layout(int items, int frames, int graphs) {
+    SearchGraphLayout w{};
+    const size_t curve = (size_t)items * graphs * frames * sizeof(float);
+    size_t at = 0;
+    w.logp = at; at += prepared_bytes(items, frames);
+    w.totals = at; at = align256(at + curve);
+    w.begins = at; at = align256(at + curve);
+    w.verdict = at; at = align256(at + (size_t)graphs * sizeof(int));
+    w.ones = at; at = align256(at + (size_t)graphs * sizeof(int));
+    w.bytes = at;
+    return w;
+}
+
+// What the lanes leave per frame of a chunk for the curve: each lane's largest D + final and its begin.  A row has 65
+// words, so the lanes that read a row each (lane = frame) meet no bank twice.
+struct SearchGraphEnds {
+    float total[CHUNK][65];
+    int begin[CHUNK][65];
+};
+
+// The frames of one pair with G states per lane: 1 for S <= 64, else 4.  `begin` is the graph's own part of arc_begin.
+// Wave-uniform control flow but for the arcs beyond the first LEAD and the lanes that write the curve.
+template <int G>
+__device__ __forceinline__ void search_graph_frames(const float4* __restrict__ src, int T, int first, int S,
+                                                    const int* __restrict__ phonemes, const float* __restrict__ stay,
+                                                    const float* __restrict__ initial,
+                                                    const float* __restrict__ final_, const int* __restrict__ begin,
+                                                    const ViterbiArcs<true>& arcs, float* __restrict__ totals,
+                                                    int* __restrict__ begins, float4 (&stage)[2][CHUNK_VEC],
+                                                    float (&dist)[2][GSTATES], int (&began)[2][GSTATES],
+                                                    SearchGraphEnds& ends, int lane)
+{
+    static_assert(G == 1 || G == 4, "a word or a 16-byte piece per lane");
+    // arcs per state a lane keeps in registers: four where it has one state (a word's first state takes the pause and
+    // three variants of the word before), two where it has four
+    constexpr int LEAD = G == 1 ? 4 : VLEAD;
+    const int n0 = lane * G, arc0 = begin[0];
+    // What the lane keeps of its states for the whole recording: the table word of viterbi_programme, the three
+    // weights, and the first LEAD arcs themselves (an arc that is not there: from the state itself at -inf, never
+    // better).  States at or above S run along on phoneme 0 without arcs, at -inf, never final.
+    int meta[G], lead[G][LEAD]; float own[G], fresh[G], fin[G], heavy[G][LEAD];
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+        const int n = n0 + k;
+        const bool state = n < S;
+        meta[k] = state ? (begin[n] - arc0) | (begin[n + 1] - begin[n]) << 16 | phonemes[first + n] << 24 : 0;
+        own[k] = state ? stay[first + n] : -INFINITY;
+        fresh[k] = state ? initial[first + n] : -INFINITY;
+        fin[k] = state ? final_[first + n] : -INFINITY;
+#pragma unroll
+        for (int j = 0; j < LEAD; ++j) {
+            lead[k][j] = n;
+            heavy[k][j] = -INFINITY;
+            if (j < degree_of(meta[k])) arcs.get(first_arc(meta[k]) + j, lead[k][j], heavy[k][j]);
+        }
+        dist[1][n] = -INFINITY;                                // D and b before frame 0
+        began[1][n] = -1;
+    }
+    float4 next[FETCH];
+    fetch(src, 0, T, lane, next);
+    stash(stage[0], lane, next);
+    __syncthreads();
+    const int used = (S + G - 1) / G;                          // the lanes that hold states
+    int buf = 0;
+    for (int t0 = 0; t0 < T; t0 += CHUNK, buf ^= 1) {
+        fetch(src, t0 + CHUNK, T, lane, next);                 // in flight while this chunk is consumed
+        const int chunk = min(CHUNK, T - t0);
+        for (int u = 0; u < chunk; ++u) {
+            const int t = t0 + u;
+            const float* e = reinterpret_cast<const float*>(stage[buf]) + u * PREP;
+            const float* before = dist[(t & 1) ^ 1];
+            const int* origin = began[(t & 1) ^ 1];
+            const float top = e[NP];                           // (a broadcast)
+            float d[G], cur[G], best[G]; int b[G];
+            if constexpr (G == 4) {
+                const float4 v = *reinterpret_cast<const float4*>(before + n0);
+                const int4 o = *reinterpret_cast<const int4*>(origin + n0);
+                d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+                b[0] = o.x; b[1] = o.y; b[2] = o.z; b[3] = o.w;
+            } else {
+                d[0] = before[n0];
+                b[0] = origin[n0];
+            }
+            // the first arcs: their D and begins are read beside the state's own, nothing waits for an arc's word
+            float came[G][LEAD]; int since[G][LEAD];
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+#pragma unroll
+                for (int j = 0; j < LEAD; ++j) {
+                    came[k][j] = before[lead[k][j]];
+                    since[k][j] = origin[lead[k][j]];
+                }
+                cur[k] = e[meta[k] >> 24] - top;
+            }
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+                best[k] = d[k] + own[k];                       // staying: what an arc has to beat
+#pragma unroll
+                for (int j = 0; j < LEAD; ++j) {
+                    const float c = came[k][j] + heavy[k][j];  // -inf + finite = -inf: never NaN
+                    const bool better = c > best[k];
+                    best[k] = better ? c : best[k];
+                    b[k] = better ? since[k][j] : b[k];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < G; ++k) {                      // what lies beyond: state by state, in list order
+                const int at = first_arc(meta[k]), degree = degree_of(meta[k]);
+                if (degree <= LEAD) continue;
+                int via = -1;                                  // the source of the candidate taken here, if any
+                auto batch = [&]<int N>(int j0) {              // arcs j0 .. j0 + N - 1, the loads ahead of the compares
+                    int p[N]; float w[N];
+#pragma unroll
+                    for (int q = 0; q < N; ++q)                // (past the last arc the last one again: never better)
+                        arcs.get(at + min(j0 + q, degree - 1), p[q], w[q]);
+#pragma unroll
+                    for (int q = 0; q < N; ++q) {
+                        const float c = before[p[q]] + w[q];
+                        const bool better = c > best[k];
+                        best[k] = better ? c : best[k];
+                        via = better ? p[q] : via;
+                    }
+                };
+                batch.template operator()<4>(LEAD);
+                for (int j0 = LEAD + 4; j0 < degree; j0 += VAHEAD) batch.template operator()<VAHEAD>(j0);
+                if (via >= 0) b[k] = origin[via];
+            }
+            // the lane's own part of the curve: the first of its largest D + final, ascending n
+            float most = -INFINITY; int opened = -1;
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+                const bool start = fresh[k] > best[k];         // a fresh start: last, and only if strictly better
+                d[k] = cur[k] + (start ? fresh[k] : best[k]);
+                b[k] = start ? t : b[k];
+                const float f = d[k] + fin[k];
+                const bool better = k == 0 || f > most;
+                most = better ? f : most;
+                opened = better ? b[k] : opened;
+            }
+            if constexpr (G == 4) {
+                *reinterpret_cast<float4*>(dist[t & 1] + n0) = make_float4(d[0], d[1], d[2], d[3]);
+                *reinterpret_cast<int4*>(began[t & 1] + n0) = make_int4(b[0], b[1], b[2], b[3]);
+            } else {
+                dist[t & 1][n0] = d[0];
+                began[t & 1][n0] = b[0];
+            }
+            ends.total[u][lane] = most;
+            ends.begin[u][lane] = opened;
+            __syncthreads();                                   // frame t+1 reads what this frame wrote
+        }
+        // the curve of the chunk, lane = frame: the first of the largest over the lanes in ascending order, which is
+        // the lowest state of equal values
+        if (lane < chunk) {
+            float most = ends.total[lane][0];
+            int opened = ends.begin[lane][0];
+#pragma unroll 4
+            for (int j = 1; j < used; ++j) {
+                const float f = ends.total[lane][j];
+                const int theirs = ends.begin[lane][j];
+                const bool better = f > most;
+                most = better ? f : most;
+                opened = better ? theirs : opened;
+            }
+            totals[t0 + lane] = most;
+            begins[t0 + lane] = most > -INFINITY ? opened : -1;
+        }
+        stash(stage[buf ^ 1], lane, next);                     // its readers passed the barrier above
+        __syncthreads();
+    }
+}
+
+// grid (graphs, items), 64 threads, `held` * 8 bytes of dynamic LDS.  G states per lane: 1 for S <= 64, else 4.
+// count = -1 for a pair that cannot be searched (its graph refused by viterbi_check or beyond 256 states or 4096 arcs,
+// its length outside [1, frames]), which touches nothing else; 0 for every other, whose curve (frames below T) is then
+// in the workspace.  ones[g] = 1 for search_pick, written here so that the call reads nothing it has not written.
+__global__ __launch_bounds__(64) void search_graph_programme(const float* __restrict__ logp, int frames,
+                                                              const int* __restrict__ lengths,
+                                                              const int* __restrict__ verdict,
+                                                              const int* __restrict__ state_begin,
+                                                              const int* __restrict__ phonemes,
+                                                              const float* __restrict__ stay,
+                                                              const float* __restrict__ initial,
+                                                              const float* __restrict__ final_,
+                                                              const int* __restrict__ arc_begin,
+                                                              const int* __restrict__ sources,
+                                                              const float* __restrict__ weights,
+                                                              float* __restrict__ totals, int* __restrict__ begins,
+                                                              int* __restrict__ ones, int* __restrict__ count)
+{
+    __shared__ float4 stage[2][CHUNK_VEC];
+    __shared__ __attribute__((aligned(16))) float dist[2][GSTATES];
+    __shared__ __attribute__((aligned(16))) int began[2][GSTATES];
+    __shared__ SearchGraphEnds ends;
+    extern __shared__ uint2 held_arcs[];
+    const int g = blockIdx.x, item = blockIdx.y, lane = threadIdx.x;
+    const size_t pair = (size_t)item * gridDim.x + g;
+    if (item == 0 && lane == 0) ones[g] = 1;
+    const int T = lengths[item];
+    bool fine = T >= 1 && T <= frames && verdict[g] != 0;
+    int first = 0, S = 0, arc0 = 0, arcs = 0;
+    if (fine) {                                                // (uniform) a good verdict: the graph's indices are sound
+        first = state_begin[g];
+        S = state_begin[g + 1] - first;
+        fine = S <= GSTATES;
+    }
+    if (fine) {
+        arc0 = arc_begin[first];
+        arcs = arc_begin[first + S] - arc0;
+        fine = arcs <= PPG_SEARCH_GRAPH_MAX_ARCS;              // (<= the dynamic LDS: no graph has more than n_arcs)
+    }
+    if (lane == 0) count[pair] = fine ? 0 : -1;
+    if (!fine) return;                                         // (uniform)
+    for (int i = lane; i < arcs; i += 64)
+        held_arcs[i] = make_uint2((uint32_t)sources[arc0 + i], __float_as_uint(weights[arc0 + i]));
+    __syncthreads();                                           // a lane keeps its states' first arcs: it reads them now
+    const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
+    const ViterbiArcs<true> in_lds{held_arcs, nullptr, nullptr, arcs};
+    float* out_totals = totals + pair * frames;
+    int* out_begins = begins + pair * frames;
+    if (S <= 64)
+        search_graph_frames<1>(src, T, first, S, phonemes, stay, initial, final_, arc_begin + first, in_lds, out_totals,
+                               out_begins, stage, dist, began, ends, lane);
+    else
+        search_graph_frames<4>(src, T, first, S, phonemes, stay, initial, final_, arc_begin + first, in_lds, out_totals,
+                               out_begins, stage, dist, began, ends, lane);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ppg_search_graph_workspace_bytes(int items, int frames, int graphs) {
+    if (items <= 0 || items > PPG_SEARCH_MAX_ITEMS || frames <= 0 || frames > PPG_SEARCH_MAX_FRAMES || graphs <= 0 ||
+        graphs > PPG_SEARCH_MAX_QUERIES)
+        return 0;
+    return search_graph_layout(items, frames, graphs).bytes;
+}
+
+int ppg_search_graph(int device, const float* ppg, int frames, int items, const int32_t* lengths, int graphs,
+                     int n_states, int n_arcs, int max_states, const int32_t* state_begin,
+                     const int32_t* state_phonemes, const float* stay, const float* initial, const float* final_,
+                     const int32_t* arc_begin, const int32_t* sources, const float* weights, int top, float threshold,
+                     int32_t* begin, int32_t* end, float* total, float* mean, int32_t* count, float* curve_total,
+                     int32_t* curve_begin, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "search_graph";
+    if (const int rc = check_common(what, ppg, frames, items, lengths, PPG_SEARCH_MAX_FRAMES, PPG_SEARCH_MAX_ITEMS))
+        return rc;
+    if (!workspace || graphs <= 0 || n_states <= 0 || n_arcs < 0 || max_states <= 0)
+        return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (graphs > PPG_SEARCH_MAX_QUERIES)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d graphs, at most %d per call", what, graphs, PPG_SEARCH_MAX_QUERIES);
+    if (max_states > PPG_VITERBI_MAX_STATES)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d states, at most %d per graph", what, max_states,
+                                 PPG_VITERBI_MAX_STATES);
+    if (n_states < graphs || (long long)n_states > (long long)graphs * max_states ||
+        (long long)n_arcs > (long long)graphs * PPG_VITERBI_MAX_ARCS)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d states and %d arcs cannot be %d graphs of 1 to %d states and at "
+                                 "most %d arcs", what, n_states, n_arcs, graphs, max_states, PPG_VITERBI_MAX_ARCS);
+    if (n_arcs > 0 && (!sources || !weights)) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (const int rc = check_words(what, {state_begin, state_phonemes, stay, initial, final_, arc_begin, begin, end,
+                                          total, mean, count},
+                                   {sources, weights, curve_total, curve_begin, ppg, lengths}))
+        return rc;
+    if (top < 1 || top > PPG_SEARCH_MAX_HITS)
+        return ppg::fail_message(PPG_EINVAL, "%s: top = %d, must be 1 .. %d", what, top, PPG_SEARCH_MAX_HITS);
+    if (threshold != threshold) return ppg::fail_message(PPG_EINVAL, "%s: the threshold is NaN", what);
+    if (!curve_total != !curve_begin)
+        return ppg::fail_message(PPG_EINVAL, "%s: curve_total and curve_begin go together", what);
+    const SearchGraphLayout w = search_graph_layout(items, frames, graphs);
+    if (const int rc = check_workspace(what, workspace, workspace_bytes, w.bytes)) return rc;
+    if (const int rc = select_device(device)) return rc;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    float* logp = reinterpret_cast<float*>(ws + w.logp);
+    float* totals = reinterpret_cast<float*>(ws + w.totals);
+    int* begins = reinterpret_cast<int*>(ws + w.begins);
+    int* verdict = reinterpret_cast<int*>(ws + w.verdict);
+    int* ones = reinterpret_cast<int*>(ws + w.ones);
+    // the arcs a wave keeps in LDS: no graph of the call has more than all of them, and none it searches more than 4096
+    const int held = n_arcs < VHELD ? n_arcs : VHELD;
+    hipLaunchKernelGGL(viterbi_check, dim3(graphs), dim3(64), 0, s, n_states, n_arcs, max_states, state_begin,
+                       state_phonemes, stay, initial, final_, arc_begin, sources, weights, verdict);
+    hipLaunchKernelGGL(align_prepare, dim3((frames + 63) / 64, items), dim3(64), 0, s, ppg, frames, lengths, logp);
+    hipLaunchKernelGGL(search_graph_programme, dim3(graphs, items), dim3(64), (size_t)held * sizeof(uint2), s, logp,
+                       frames, lengths, verdict, state_begin, state_phonemes, stay, initial, final_, arc_begin, sources,
+                       weights, totals, begins, ones, count);
+    hipLaunchKernelGGL(search_pick, dim3(graphs, items), dim3(64), 0, s, frames, lengths, ones, top, threshold, totals,
+                       begins, begin, end, total, mean, count, curve_total, curve_begin);
     return launched(what);
 }
 

@@ -193,6 +193,13 @@ SYMBOLS = {
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_size_t, ctypes.c_void_p]),
+    'ppg_search_graph_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_search_graph': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'ppg_search_stream_state_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'ppg_search_stream_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'ppg_search_stream_reset': (ctypes.c_int, [
@@ -1257,6 +1264,116 @@ def search_items(ppg, lengths, table, counts, top=1, threshold=-math.inf, want_c
                     for out, part in zip(outputs, parts):
                         out[at:at + rows, low:low + columns].copy_(part)
     return begin, end, total, mean, count, curve
+
+
+SEARCH_GRAPH_MAX_STATES = 256    # PPG_SEARCH_GRAPH_MAX_STATES, per graph
+SEARCH_GRAPH_MAX_ARCS = 4096     # PPG_SEARCH_GRAPH_MAX_ARCS, per graph
+SEARCH_GRAPH_MAX_GRAPHS = 65535  # = PPG_SEARCH_MAX_QUERIES, per call of the library
+SEARCH_GRAPH_WORKSPACE_BYTES = 1 << 30  # a larger batch runs as several calls, each within this much workspace
+
+
+def search_graph_items(ppg, lengths, state_begin, phonemes, stay, initial, final, arc_begin, sources, weights, top=1,
+                       threshold=-math.inf, want_curve=False, max_states=None,
+                       workspace_bytes=SEARCH_GRAPH_WORKSPACE_BYTES):
+    """Phrase search over graphs (ppg_search_graph): every graph in every recording ppg[b, :, :lengths[b]].  The graphs
+    travel packed as `viterbi_items` takes them; state_begin and arc_begin are host integers or CPU tensors (a batch
+    that is split needs their values here).  Nothing of the graphs is checked: the device checks them, and a pair
+    whose graph it refuses, whose graph has more than SEARCH_GRAPH_MAX_STATES states or SEARCH_GRAPH_MAX_ARCS arcs, or
+    whose length is impossible has count -1.  max_states bounds every graph's states for the device's check (None: the
+    library's limit or the number of states, whichever is less).  A batch that needs more than `workspace_bytes` runs
+    as several calls: graphs in groups beside one recording's prepared frames, then recordings in groups.  The outputs
+    are `search_items`' with the graphs in the place of the queries.  Nothing here waits for the device."""
+    if not ppg.is_cuda:
+        raise PpgError('ppgs_amd: the post-ops work on HIP device tensors')
+    x = ppg.to(torch.float32).contiguous()
+    if x.dim() != 3 or x.shape[1] != 40 or x.shape[0] < 1:
+        raise ValueError(f'PPGs must be (items >= 1, 40, frames), got {tuple(x.shape)}')
+    items, frames = x.shape[0], x.shape[2]
+    if not 1 <= frames <= SEARCH_MAX_FRAMES:
+        raise ValueError(f'search_graph takes 1 to {SEARCH_MAX_FRAMES} frames, got {frames}')
+    lengths = [int(v) for v in lengths]
+    if len(lengths) != items:
+        raise ValueError(f'{len(lengths)} lengths for {items} items')
+    device = x.device
+    host = {'state_begin': torch.as_tensor(state_begin), 'arc_begin': torch.as_tensor(arc_begin)}
+
+    def words(tensor, dtype, name):
+        tensor = torch.as_tensor(tensor)
+        if tensor.dim() != 1:
+            raise ValueError(f'{name} must be one-dimensional, got {tuple(tensor.shape)}')
+        return tensor.to(device=device, dtype=dtype).contiguous()
+    state_begin, arc_begin = (words(host[name], torch.int32, name) for name in ('state_begin', 'arc_begin'))
+    phonemes, sources = words(phonemes, torch.int32, 'phonemes'), words(sources, torch.int32, 'sources')
+    stay, initial = words(stay, torch.float32, 'stay'), words(initial, torch.float32, 'initial')
+    final, weights = words(final, torch.float32, 'final'), words(weights, torch.float32, 'weights')
+    graphs, count, arcs = state_begin.shape[0] - 1, phonemes.shape[0], sources.shape[0]
+    if graphs < 1 or count < 1:
+        raise ValueError('search_graph takes at least one graph of at least one state')
+    for name, tensor, size in (('stay', stay, count), ('initial', initial, count), ('final', final, count),
+                               ('arc_begin', arc_begin, count + 1), ('weights', weights, arcs)):
+        if tensor.shape[0] != size:
+            raise ValueError(f'{name} has {tensor.shape[0]} entries, {size} expected')
+    if max_states is None:
+        max_states = min(VITERBI_MAX_STATES, count)
+    if not 1 <= max_states <= VITERBI_MAX_STATES:
+        raise ValueError(f'search_graph takes max_states from 1 to {VITERBI_MAX_STATES}, got {max_states}')
+    top, threshold = int(top), float(threshold)
+    if not 1 <= top <= SEARCH_MAX_HITS:
+        raise ValueError(f'top must be 1 to {SEARCH_MAX_HITS}, got {top}')
+    if threshold != threshold:
+        raise ValueError('the threshold is NaN')
+    lengths = torch.tensor(lengths, dtype=torch.int32).to(device)
+    shape = (items, graphs, top)
+    begin = torch.empty(shape, dtype=torch.int32, device=device)
+    end = torch.empty(shape, dtype=torch.int32, device=device)
+    total = torch.empty(shape, dtype=torch.float32, device=device)
+    mean = torch.empty(shape, dtype=torch.float32, device=device)
+    hits = torch.empty((items, graphs), dtype=torch.int32, device=device)
+    curve = None
+    if want_curve:
+        curve = (torch.full((items, graphs, frames), -math.inf, dtype=torch.float32, device=device),
+                 torch.full((items, graphs, frames), -1, dtype=torch.int32, device=device))
+    lib = library()
+    bytes_for = lib.ppg_search_graph_workspace_bytes
+    # graphs per call: one recording's prepared frames (176 bytes a frame), 8 bytes per pair and frame of curve, 8 per
+    # graph of verdict and ones, five blocks rounded up to 256 bytes; then recordings
+    some = max(1, min(graphs, SEARCH_GRAPH_MAX_GRAPHS, (int(workspace_bytes) - 1280 - 176 * frames) // (8 * frames + 8)))
+    group = max(1, min(items, SEARCH_MAX_ITEMS, int(workspace_bytes) // bytes_for(1, frames, some)))
+    size = bytes_for(group, frames, some)
+    workspace = torch.empty((size,), dtype=torch.uint8, device=device)
+    outputs = (begin, end, total, mean, hits) + (curve or ())
+    if some < graphs:                                           # the packed graphs of a group count from its own first
+        first_state, first_arc = host['state_begin'].tolist(), host['arc_begin'].tolist()
+
+    def pointer(tensor):
+        return tensor.data_ptr() if tensor is not None else None
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for at in range(0, items, group):
+            rows = min(group, items - at)
+            for low in range(0, graphs, some):
+                columns = min(some, graphs - low)
+                if columns == graphs:                           # every graph: straight into the outputs
+                    parts = [out[at:] for out in outputs]
+                    s0, s1, a0, a1 = 0, count, 0, arcs
+                    state_part, arc_part = state_begin, arc_begin
+                else:
+                    parts = [out[at:at + rows, low:low + columns].contiguous() for out in outputs]
+                    s0, s1 = first_state[low], first_state[low + columns]
+                    a0, a1 = first_arc[s0], first_arc[s1]
+                    state_part = (state_begin[low:low + columns + 1] - s0).contiguous()
+                    arc_part = (arc_begin[s0:s1 + 1] - a0).contiguous()
+                slots = parts + [None] * (7 - len(parts))          # no curve: two NULL pointers
+                _check(lib.ppg_search_graph(
+                    device.index, x[at:].data_ptr(), frames, rows, lengths[at:].data_ptr(), columns, s1 - s0, a1 - a0,
+                    max_states, state_part.data_ptr(), phonemes[s0:].data_ptr(), stay[s0:].data_ptr(),
+                    initial[s0:].data_ptr(), final[s0:].data_ptr(), arc_part.data_ptr(),
+                    sources[a0:].data_ptr() if a1 > a0 else None, weights[a0:].data_ptr() if a1 > a0 else None, top,
+                    threshold, *[pointer(part) for part in slots], workspace.data_ptr(), size, stream))
+                if columns != graphs:
+                    for out, part in zip(outputs, parts):
+                        out[at:at + rows, low:low + columns].copy_(part)
+    return begin, end, total, mean, hits, curve
 
 
 def search_stream_state(device, streams, queries, most):
