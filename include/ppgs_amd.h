@@ -1005,6 +1005,74 @@ int ppg_search_stream_flush(int device, void* state, int streams, int queries, i
                             int32_t* begin, int32_t* end, float* total, float* mean, int32_t* count, void* stream);
 
 /*
+ * Live phrase search over a phoneme graph: ppg_search_graph carried across the pushes of a stream, as ppg_search_stream_*
+ * carries ppg_search (a keyword spotter on a live PPG with pronunciation variants, optional pauses between words and
+ * droppable consonants in one query).  A push does work proportional to its own frames.  Not in the reference.
+ *
+ * One pair is a stream and a graph; every graph runs on every stream (there is no `which_graph`).  A stream has a
+ * position p, the frames received since its last reset; frame indices are absolute.
+ *   Curve.  ppg_search_graph's recurrence, unchanged: the same prepared frame and emission, the candidates in the same
+ *   order (stay, the in-arcs in list order, the fresh start last) under strict >, fp32 additions in frame order.  A fresh
+ *   start at frame t of a push sets b = p + t.  curve_total is the largest D + final, the lowest state on ties, and
+ *   curve_begin that state's begin, -1 where the total is -inf.  For any split of a recording into pushes the
+ *   concatenated curve equals ppg_search_graph's curve of the recording bit for bit, pushes of 0 and 1 frames included.
+ *   Online detector, flush and reset.  ppg_search_stream_*'s, word for word: one threshold and one patience per call,
+ *   `taken`, at most one pending hit; flush emits the pending hit and keeps the curve state and the position; reset
+ *   returns a stream to position 0 with every state at -inf / -1, taken = 0 and nothing pending.
+ *   Under a chain (as in ppg_search_graph) every output equals ppg_search_stream_*'s for that query bit for bit.
+ *
+ * The caller owns the state (device memory, 16-byte aligned, ppg_search_graph_stream_state_bytes(streams, graphs,
+ * max_states) bytes, to be opened before its first push); there is no handle.  Five blocks, each 256-byte aligned: the
+ * position of every stream (int32), the verdict on every graph (int32), the detector of every pair (8 words, as in
+ * ppg_search_stream_*), then D and b of every pair (a row of 64 words each where max_states <= 64, 256 above).  A state
+ * belongs to one (streams, graphs, max_states) and the graphs it was opened with.
+ *
+ * ppg_search_graph_stream_open: checks every graph as ppg_viterbi does, stores the verdicts in the state and resets
+ * every stream.  graphs .. weights are the packed graphs and their host integers exactly as ppg_viterbi takes them;
+ * max_states is 1 .. PPG_VITERBI_MAX_STATES and bounds every graph.  The same arrays go to every push: a push goes by
+ * the stored verdicts and checks nothing of a graph again (a source it reads is clamped into the graph's states).
+ * ppg_search_graph_stream_push: every stream takes lengths[i] frames.
+ *   ppg, frames, streams, lengths, threshold, patience, cap, begin, end, total, mean, count, curve_total, curve_begin,
+ *   workspace : as ppg_search_stream_push with `graphs` in the place of `queries`: the shapes, the sentinels (-1, -1,
+ *                     NaN, NaN) and count > cap for a push that overflowed.  The workspace has at least
+ *                     ppg_search_graph_stream_workspace_bytes(streams, frames, graphs) bytes: the prepared frames.
+ *   count = -1      : for a pair whose graph was refused at open or has more than PPG_SEARCH_GRAPH_MAX_STATES states or
+ *                     PPG_SEARCH_GRAPH_MAX_ARCS arcs, whose length is outside [0, frames], or whose position would pass
+ *                     INT32_MAX: its state and its other outputs are left untouched, and its stream's position stays if
+ *                     the length or the position is at fault.
+ * ppg_search_graph_stream_flush and _reset: as ppg_search_stream_flush and _reset, (streams, graphs) outputs, `which`
+ * device int32[streams] flags or NULL for all.
+ * Kernel launches on `stream` only: no allocation, synchronisation or copy.  Every byte a kernel reads was written by
+ * open, reset or an earlier kernel of the same sequence of calls.  The position of a stream is advanced once per push by
+ * a launch of its own after the pairs have run.
+ * PPG_EINVAL, and nothing launched, for what ppg_search_stream_push and ppg_search_graph refuse on the host: a NaN
+ * threshold, patience < 0, cap < 1, frames outside 1 .. PPG_SEARCH_MAX_FRAMES, more than PPG_SEARCH_MAX_ITEMS streams or
+ * PPG_SEARCH_MAX_QUERIES graphs, max_states beyond PPG_VITERBI_MAX_STATES, n_states or n_arcs that cannot be, one curve
+ * pointer without the other, an unaligned or short workspace, an unaligned state, a NULL or unaligned input or output.
+ * The two *_bytes helpers are host-only and return 0 for impossible arguments.
+ */
+size_t ppg_search_graph_stream_state_bytes(int streams, int graphs, int max_states);
+size_t ppg_search_graph_stream_workspace_bytes(int streams, int frames, int graphs);
+int ppg_search_graph_stream_open(int device, void* state, int streams, int graphs, int n_states, int n_arcs,
+                                 int max_states, const int32_t* state_begin, const int32_t* state_phonemes,
+                                 const float* stay, const float* initial, const float* final_,
+                                 const int32_t* arc_begin, const int32_t* sources, const float* weights,
+                                 void* stream);
+int ppg_search_graph_stream_reset(int device, void* state, int streams, int graphs, int max_states,
+                                  const int32_t* which, void* stream);
+int ppg_search_graph_stream_push(int device, void* state, const float* ppg, int frames, int streams,
+                                 const int32_t* lengths, int graphs, int n_states, int n_arcs, int max_states,
+                                 const int32_t* state_begin, const int32_t* state_phonemes, const float* stay,
+                                 const float* initial, const float* final_, const int32_t* arc_begin,
+                                 const int32_t* sources, const float* weights, float threshold, int patience, int cap,
+                                 int32_t* begin, int32_t* end, float* total, float* mean, int32_t* count,
+                                 float* curve_total, int32_t* curve_begin, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+int ppg_search_graph_stream_flush(int device, void* state, int streams, int graphs, int max_states,
+                                  const int32_t* which, int32_t* begin, int32_t* end, float* total, float* mean,
+                                  int32_t* count, void* stream);
+
+/*
  * Live phoneme recognition: ppg_recognize carried across the pushes of a stream (captions, a pronunciation tutor, an
  * endpointer on a live PPG).  A push does work proportional to its own frames and to the frames whose label can still
  * change, whatever the age of the stream, and gives out the runs that have become final.  Not in the reference.

@@ -150,7 +150,7 @@ frame's maximum, which no path through a fixed span can change.
     hits = ppgs_amd.alignment.search_graph(ppg, graph, top=5, threshold=-1.)
     b, e = int(hits.begin[0]), int(hits.end[0])
     said = [variant_of[n] for n in ppgs_amd.alignment.viterbi(ppg[:, b:e], graph).states.tolist()]
-Not here: a live form, graphs over 256 states (a word loop belongs to `viterbi`).
+Not here: graphs over 256 states (a word loop belongs to `viterbi`).
 
 Live phrase search (`SearchStream`, ppg_search_stream_*): the same curve carried across the pushes of a stream, bit for
 bit whatever the push sizes, with an online rule that gives a hit out once nothing later can overlap and beat it.
@@ -158,6 +158,13 @@ bit whatever the push sizes, with an online rule that gives a hit out once nothi
     spotter = ppgs_amd.alignment.SearchStream(['hh', 'ah', 'l', 'ow'], threshold=-1., patience=25)
     hits = spotter.push(frames)          # (40, k) as a stream emits them, k >= 0; Hits of this push
     last = spotter.flush()
+
+Live phrase search over a graph (`SearchGraphStream`, ppg_search_graph_stream_*): `search_graph`'s curve carried across
+the pushes in the same way (a fresh start at frame t of a push at position p begins at p + t), under the same online
+rule; on `chain_graph(s)` every output is `SearchStream(s)`'s bit for bit.
+
+    spotter = ppgs_amd.alignment.SearchGraphStream(graph, threshold=-1.)
+    hits = spotter.push(frames)          # GraphHits of this push
 
 Live phoneme recognition (`RecognizeStream`, ppg_recognize_stream_*): `recognize` carried across the pushes of a stream.
 One stream has a position p, the frames received since the last reset (frame indices are absolute); a commit point c,
@@ -1110,6 +1117,49 @@ def search(ppg, phonemes, lengths=None, top=1, threshold=None, curve=False):
                 None if curves is None else (drop(curves[0]), drop(curves[1])))
 
 
+def _search_graphs(graphs):
+    """The graphs of a search, one Graph or a list of them: (several, the checked graphs)."""
+    several = isinstance(graphs, (list, tuple)) and not isinstance(graphs, Graph)
+    values = list(graphs) if several else [graphs]
+    if not 1 <= len(values) <= SEARCH_GRAPH_MAX_GRAPHS:
+        raise ValueError(f'search_graph takes 1 to {SEARCH_GRAPH_MAX_GRAPHS} graphs, got {len(values)}')
+    packed = [_checked_graph(value) for value in values]
+    for index, value in enumerate(packed):
+        count, arcs = value.phonemes.shape[0], value.sources.shape[0]
+        if count > SEARCH_GRAPH_MAX_STATES or arcs > SEARCH_GRAPH_MAX_ARCS:
+            raise ValueError(f'search_graph takes graphs of at most {SEARCH_GRAPH_MAX_STATES} states and '
+                             f'{SEARCH_GRAPH_MAX_ARCS} arcs, graph {index} has {count} and {arcs}')
+    return several, packed
+
+
+def shortest_match(graph):
+    """The fewest frames a match of `graph` can span: the fewest states on any path from a state with a finite
+    `initial` to a state with a finite `final` (a breadth-first search over the arcs; staying adds nothing), at least
+    1; 1 for a graph that has no such path, which never matches anything.  Host only."""
+    count = graph.phonemes.shape[0]
+    offsets, sources = graph.offsets.tolist(), graph.sources.tolist()
+    open_arc = (graph.weights > -math.inf).tolist()
+    out = [[] for _ in range(count)]
+    for n in range(count):
+        for j in range(offsets[n], offsets[n + 1]):
+            if open_arc[j]:
+                out[sources[j]].append(n)
+    final = (graph.final > -math.inf).tolist()
+    reached = [bool(value) for value in (graph.initial > -math.inf).tolist()]
+    front, states = [n for n in range(count) if reached[n]], 1
+    while front:
+        if any(final[n] for n in front):
+            return states
+        following = []
+        for p in front:
+            for n in out[p]:
+                if not reached[n]:
+                    reached[n] = True
+                    following.append(n)
+        front, states = following, states + 1
+    return 1
+
+
 def search_graph(ppg, graphs, lengths=None, top=1, threshold=None, curve=False):
     """Find where a path through a Graph is said in `ppg`: GraphHits(begin, end, total, mean, count, curve).
 
@@ -1123,16 +1173,7 @@ def search_graph(ppg, graphs, lengths=None, top=1, threshold=None, curve=False):
     if not batched and lengths is not None:
         raise ValueError('lengths go with a batch: slice a single PPG instead')
     lengths = _lengths(lengths, batch, frames)
-    several = isinstance(graphs, (list, tuple)) and not isinstance(graphs, Graph)
-    values = list(graphs) if several else [graphs]
-    if not 1 <= len(values) <= SEARCH_GRAPH_MAX_GRAPHS:
-        raise ValueError(f'search_graph takes 1 to {SEARCH_GRAPH_MAX_GRAPHS} graphs, got {len(values)}')
-    packed = [_checked_graph(value) for value in values]
-    for index, value in enumerate(packed):
-        count, arcs = value.phonemes.shape[0], value.sources.shape[0]
-        if count > SEARCH_GRAPH_MAX_STATES or arcs > SEARCH_GRAPH_MAX_ARCS:
-            raise ValueError(f'search_graph takes graphs of at most {SEARCH_GRAPH_MAX_STATES} states and '
-                             f'{SEARCH_GRAPH_MAX_ARCS} arcs, graph {index} has {count} and {arcs}')
+    several, packed = _search_graphs(graphs)
     if isinstance(top, bool) or not isinstance(top, int) or not 1 <= top <= SEARCH_MAX_HITS:
         raise ValueError(f'top must be an integer from 1 to {SEARCH_MAX_HITS}, got {top!r}')
     threshold = -math.inf if threshold is None else float(threshold)
@@ -1188,6 +1229,17 @@ class SearchStream:
 
     def __init__(self, phonemes, threshold, patience=25, batch=None, curve=False, device=None):
         self._several, sequences = _queries(phonemes)
+        self._detector(threshold, patience, batch, curve, device)
+        self._counts = [len(sequence) for sequence in sequences]
+        self._most = max(self._counts)
+        self._pairs, self._shortest = len(self._counts), min(self._counts)
+        self._host_table = torch.tensor([sequence + [-1] * (self._most - len(sequence)) for sequence in sequences],
+                                        dtype=torch.int32)
+        self._table = self._device_counts = self._names = None
+
+    def _detector(self, threshold, patience, batch, curve, device):
+        """What a live search has whatever its queries are: the detector's two numbers, the streams and their host
+        side."""
         threshold = float(threshold)
         if math.isnan(threshold):
             raise ValueError('the threshold is NaN')
@@ -1198,13 +1250,9 @@ class SearchStream:
             raise ValueError(f'batch must be None or 1 to {engine.SEARCH_MAX_ITEMS} streams, got {batch!r}')
         self.threshold, self.patience, self.batch, self.curve = threshold, patience, batch, bool(curve)
         self._streams = 1 if batch is None else batch
-        self._counts = [len(sequence) for sequence in sequences]
-        self._most = max(self._counts)
-        self._host_table = torch.tensor([sequence + [-1] * (self._most - len(sequence)) for sequence in sequences],
-                                        dtype=torch.int32)
         self._gpu = device
         self._position = [0] * self._streams
-        self._state = self._workspace = self._table = self._device_counts = self._names = None
+        self._state = self._workspace = None
         self._uniform, self._flags = {}, {}
 
     @property
@@ -1270,7 +1318,7 @@ class SearchStream:
             if position + value > 2 ** 31 - 1:
                 raise ValueError(f'a stream takes at most {2 ** 31 - 1} frames between resets, got {position} + {value}')
         device = self._ensure(ppg)
-        queries = len(self._counts)
+        queries = self._pairs
         if frames == 0:
             shape = (self._streams, queries, 0)
             return self._hits(
@@ -1290,26 +1338,97 @@ class SearchStream:
             on_device = self._uniform[frames]
         else:                                                            # through pinned memory: the copy does not wait
             on_device = torch.tensor(own, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
-        need = engine.library().ppg_search_stream_workspace_bytes(self._streams, frames, queries)
+        need = self._workspace_bytes(frames)
         if self._workspace is None or self._workspace.numel() < need:
             self._workspace = torch.empty((need,), dtype=torch.uint8, device=device)
-        cap = frames // min(self._counts) + 2
-        begin, end, total, mean, count, curves = engine.search_stream_push(
-            self._state, x, on_device, self._table, self._device_counts, self.threshold, self.patience, cap,
-            self._workspace, self.curve)
+        cap = frames // self._shortest + 2
+        begin, end, total, mean, count, curves = self._push_piece(x, on_device, cap)
         self._position = [position + value for position, value in zip(self._position, own)]
         return self._hits(begin, end, total, mean, count, curves)
 
     def flush(self, item=None):
         which = self._which(item)
         self._ensure()
-        return self._hits(*engine.search_stream_flush(self._state, self._streams, len(self._counts), self._most, which))
+        return self._hits(*self._flush_all(which))
 
     def reset(self, item=None):
         which = self._which(item)
         self._ensure()
-        engine.search_stream_reset(self._state, self._streams, len(self._counts), self._most, which)
+        self._reset_all(which)
         self._position = [0 if item is None or b == item else position for b, position in enumerate(self._position)]
+
+    # what SearchGraphStream replaces: the library's calls
+    def _workspace_bytes(self, frames):
+        return engine.library().ppg_search_stream_workspace_bytes(self._streams, frames, self._pairs)
+
+    def _push_piece(self, x, lengths, cap):
+        return engine.search_stream_push(self._state, x, lengths, self._table, self._device_counts, self.threshold,
+                                         self.patience, cap, self._workspace, self.curve)
+
+    def _flush_all(self, which):
+        return engine.search_stream_flush(self._state, self._streams, self._pairs, self._most, which)
+
+    def _reset_all(self, which):
+        engine.search_stream_reset(self._state, self._streams, self._pairs, self._most, which)
+
+
+class SearchGraphStream(SearchStream):
+    """`search_graph` on a live stream: SearchStream with graphs as the queries, so that a spotter on a live stream has
+    pronunciation variants, optional pauses between words and droppable consonants in one query.
+
+        graph = ppgs_amd.alignment.phrase_graph([[['iy', 'dh', 'er'], ['ay', 'dh', 'er']], [['w', 'ey']]])[0]
+        spotter = ppgs_amd.alignment.SearchGraphStream(graph, threshold=-1.)
+        for piece in pieces:                                     # each (40, k), k >= 0
+            for start, end, total, mean in ppgs_amd.alignment.hit_segments(spotter.push(piece)): ...
+        last = spotter.flush()
+
+    `graphs` is one Graph or a list of Q of them, validated as `search_graph` validates them (at most 256 states and
+    4096 arcs each); every graph runs on every stream.  The curve is `search_graph`'s: whatever the sizes of the pushes,
+    the pushed frames' curve values are those of `search_graph(whole recording, ..., curve=True)` at the same frames, bit
+    for bit, with begins that count from the last reset.  `threshold`, `patience`, `batch`, `curve`, `device`, the
+    online rule, push, flush, reset and `position` are SearchStream's; push and flush return `GraphHits` with the
+    dropped axes of `search_graph`, which `hit_segments` takes as it is.  cap = F // Lmin + 2, Lmin the fewest states
+    on a path from a state that may start a match to one that may end it (`shortest_match`), the least over the graphs:
+    hits are disjoint, each spans at least Lmin frames, and at most one was pending before the push.  On
+    `chain_graph(s)` every output equals `SearchStream(s)`'s bit for bit.  Nothing here waits for the device."""
+
+    def __init__(self, graphs, threshold, patience=25, batch=None, curve=False, device=None):
+        self._several, packed = _search_graphs(graphs)
+        self._detector(threshold, patience, batch, curve, device)
+        counts, state_begin, arc_begin, joined = _joined_graphs(packed)
+        self._graphs = engine.PackedGraphs(
+            len(packed), sum(counts), int(arc_begin[-1]), max(counts), state_begin.to(torch.int32),
+            joined('phonemes').to(torch.int32), joined('stay').to(torch.float32), joined('initial').to(torch.float32),
+            joined('final').to(torch.float32), arc_begin.to(torch.int32), joined('sources').to(torch.int32),
+            joined('weights').to(torch.float32))
+        self._pairs, self._shortest = len(packed), min(shortest_match(value) for value in packed)
+        self._weights = None
+
+    def _ensure(self, tensor=None):
+        if self._state is None:
+            device = core.device_for(self._gpu, tensor)
+            self._weights = engine.PackedGraphs(*[value.to(device).contiguous() if torch.is_tensor(value) else value
+                                                  for value in self._graphs])
+            with torch.cuda.device(device):
+                self._state = engine.search_graph_stream_state(device, self._streams, self._weights)
+        return self._state.device
+
+    def _hits(self, begin, end, total, mean, count, curves=None):
+        return GraphHits(self._drop(begin), self._drop(end), self._drop(total), self._drop(mean), self._drop(count),
+                         None if curves is None else (self._drop(curves[0]), self._drop(curves[1])))
+
+    def _workspace_bytes(self, frames):
+        return engine.library().ppg_search_graph_stream_workspace_bytes(self._streams, frames, self._pairs)
+
+    def _push_piece(self, x, lengths, cap):
+        return engine.search_graph_stream_push(self._state, x, lengths, self._weights, self.threshold, self.patience,
+                                               cap, self._workspace, self.curve)
+
+    def _flush_all(self, which):
+        return engine.search_graph_stream_flush(self._state, self._streams, self._pairs, self._weights.max_states, which)
+
+    def _reset_all(self, which):
+        engine.search_graph_stream_reset(self._state, self._streams, self._pairs, self._weights.max_states, which)
 
 
 class RecognizeStream:

@@ -4,8 +4,9 @@
 // recogniser, the best path through all 40 phonemes under a transition model (ppg_recognize), and last
 // that recogniser carried across the pushes of a stream (ppg_recognize_stream_*).  The best path through a
 // graph of phoneme states (ppg_viterbi) follows the live recogniser.  The phrase search over such a graph
-// (ppg_search_graph) stands at the very end of the file, behind the host entries of all the others, with
-// its own host entries.
+// (ppg_search_graph) stands at the very end of the file, behind the host entries of all the others, and
+// behind it that search carried across the pushes of a stream (ppg_search_graph_stream_*): the two share
+// one body, `search_graph_frames`, and their host entries close the file.
 //
 //   e[t, n] = logf(min(max(P[s[n], t], 1e-8), 1 - 1e-8))                      (the clamp of ppg_distance)
 //   D[0, 0] = e[0, 0];  D[0, n > 0] = -inf
@@ -3295,6 +3296,24 @@ inline SearchGraphLayout search_graph_layout(int items, int frames, int graphs) 
     return w;
 }
 
+// the packed graphs of a search, whole-recording or live: as ppg_viterbi takes them, at most PPG_SEARCH_MAX_QUERIES
+int check_search_graphs(const char* what, int graphs, int n_states, int n_arcs, int max_states, const void* sources,
+                        const void* weights) {
+    if (graphs <= 0 || n_states <= 0 || n_arcs < 0 || max_states <= 0)
+        return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (graphs > PPG_SEARCH_MAX_QUERIES)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d graphs, at most %d per call", what, graphs, PPG_SEARCH_MAX_QUERIES);
+    if (max_states > PPG_VITERBI_MAX_STATES)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d states, at most %d per graph", what, max_states,
+                                 PPG_VITERBI_MAX_STATES);
+    if (n_states < graphs || (long long)n_states > (long long)graphs * max_states ||
+        (long long)n_arcs > (long long)graphs * PPG_VITERBI_MAX_ARCS)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d states and %d arcs cannot be %d graphs of 1 to %d states and at "
+                                 "most %d arcs", what, n_states, n_arcs, graphs, max_states, PPG_VITERBI_MAX_ARCS);
+    if (n_arcs > 0 && (!sources || !weights)) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    return PPG_OK;
+}
+
 // What the lanes leave per frame of a chunk for the curve: each lane's largest D + final and its begin.  A row has 65
 // words, so the lanes that read a row each (lane = frame) meet no bank twice.
 struct SearchGraphEnds {
@@ -3302,9 +3321,22 @@ struct SearchGraphEnds {
     int begin[CHUNK][65];
 };
 
+// What a push of a live search over a graph carries into the search of one pair and out of it again.
+struct GraphCarry {
+    float* d; int* b;                         // the pair's D and b between pushes: a row of 64 or 256 words each
+    int base;                                 // the stream's position: frame t of the push is frame base + t of the stream
+    Detector* det; Events* out;               // the pair's detector, run by lane 0, and this push's events
+    float threshold; int patience;
+};
+
 // The frames of one pair with G states per lane: 1 for S <= 64, else 4.  `begin` is the graph's own part of arc_begin.
-// Wave-uniform control flow but for the arcs beyond the first LEAD and the lanes that write the curve.
-template <int G>
+// Live: one push of T >= 1 frames of a stream: D and b come from `live` and go back there (the states at or above S
+// run along at -inf / -1 as ever), a fresh start begins at the stream's position + t, the curve is written only if
+// asked for, and after every chunk's reduction lane 0 runs the detector over the chunk's frames in order.  Otherwise
+// `live` is unused: every state starts at -inf / -1 and frames count from 0.  One body, so the pushes of a stream give
+// the curve of the whole recording bit for bit.
+// Wave-uniform control flow but for the arcs beyond the first LEAD, the lanes that write the curve and the detector.
+template <int G, bool Live>
 __device__ __forceinline__ void search_graph_frames(const float4* __restrict__ src, int T, int first, int S,
                                                     const int* __restrict__ phonemes, const float* __restrict__ stay,
                                                     const float* __restrict__ initial,
@@ -3312,9 +3344,10 @@ __device__ __forceinline__ void search_graph_frames(const float4* __restrict__ s
                                                     const ViterbiArcs<true>& arcs, float* __restrict__ totals,
                                                     int* __restrict__ begins, float4 (&stage)[2][CHUNK_VEC],
                                                     float (&dist)[2][GSTATES], int (&began)[2][GSTATES],
-                                                    SearchGraphEnds& ends, int lane)
+                                                    SearchGraphEnds& ends, const GraphCarry& live, int lane)
 {
     static_assert(G == 1 || G == 4, "a word or a 16-byte piece per lane");
+    const int base = Live ? live.base : 0;
     // arcs per state a lane keeps in registers: four where it has one state (a word's first state takes the pause and
     // three variants of the word before), two where it has four
     constexpr int LEAD = G == 1 ? 4 : VLEAD;
@@ -3337,8 +3370,10 @@ __device__ __forceinline__ void search_graph_frames(const float4* __restrict__ s
             heavy[k][j] = -INFINITY;
             if (j < degree_of(meta[k])) arcs.get(first_arc(meta[k]) + j, lead[k][j], heavy[k][j]);
         }
-        dist[1][n] = -INFINITY;                                // D and b before frame 0
-        began[1][n] = -1;
+        // D and b before frame 0, which reads buffer 1: of a push they are the row's words n0 .. n0 + G - 1, which
+        // the lane itself stored (or the reset did: the rows are whole, so no lane asks whether n < S)
+        dist[1][n] = Live ? live.d[n] : -INFINITY;
+        began[1][n] = Live ? live.b[n] : -1;
     }
     float4 next[FETCH];
     fetch(src, 0, T, lane, next);
@@ -3415,7 +3450,7 @@ __device__ __forceinline__ void search_graph_frames(const float4* __restrict__ s
             for (int k = 0; k < G; ++k) {
                 const bool start = fresh[k] > best[k];         // a fresh start: last, and only if strictly better
                 d[k] = cur[k] + (start ? fresh[k] : best[k]);
-                b[k] = start ? t : b[k];
+                b[k] = start ? base + t : b[k];
                 const float f = d[k] + fin[k];
                 const bool better = k == 0 || f > most;
                 most = better ? f : most;
@@ -3434,6 +3469,7 @@ __device__ __forceinline__ void search_graph_frames(const float4* __restrict__ s
         }
         // the curve of the chunk, lane = frame: the first of the largest over the lanes in ascending order, which is
         // the lowest state of equal values
+        float reach = -INFINITY; int since = -1;               // (Live) frame t0 + lane's two curve values
         if (lane < chunk) {
             float most = ends.total[lane][0];
             int opened = ends.begin[lane][0];
@@ -3445,11 +3481,33 @@ __device__ __forceinline__ void search_graph_frames(const float4* __restrict__ s
                 most = better ? f : most;
                 opened = better ? theirs : opened;
             }
-            totals[t0 + lane] = most;
-            begins[t0 + lane] = most > -INFINITY ? opened : -1;
+            if (!Live || totals) {
+                totals[t0 + lane] = most;
+                begins[t0 + lane] = most > -INFINITY ? opened : -1;
+            }
+            if constexpr (Live) {
+                reach = most;
+                since = most > -INFINITY ? opened : -1;
+            }
+        }
+        if constexpr (Live) {
+            // The detector takes the frames in order, and the reduction left frame t0 + u in lane u: lane 0 walks the
+            // chunk, each frame's pair read across the lanes with a uniform index (two v_readlane, no LDS, no barrier).
+            for (int u = 0; u < chunk; ++u) {                  // (uniform)
+                const float sum = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(reach), u));
+                const int first = __builtin_amdgcn_readlane(since, u);
+                if (lane == 0) detect(*live.det, *live.out, base + t0 + u, sum, first, live.threshold, live.patience);
+            }
         }
         stash(stage[buf ^ 1], lane, next);                     // its readers passed the barrier above
         __syncthreads();
+    }
+    if constexpr (Live) {                                      // the last frame wrote buffer (T - 1) & 1: the lane's own words
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            live.d[n0 + k] = dist[(T - 1) & 1][n0 + k];
+            live.b[n0 + k] = began[(T - 1) & 1][n0 + k];
+        }
     }
 }
 
@@ -3502,11 +3560,137 @@ __global__ __launch_bounds__(64) void search_graph_programme(const float* __rest
     float* out_totals = totals + pair * frames;
     int* out_begins = begins + pair * frames;
     if (S <= 64)
-        search_graph_frames<1>(src, T, first, S, phonemes, stay, initial, final_, arc_begin + first, in_lds, out_totals,
-                               out_begins, stage, dist, began, ends, lane);
+        search_graph_frames<1, false>(src, T, first, S, phonemes, stay, initial, final_, arc_begin + first, in_lds,
+                                      out_totals, out_begins, stage, dist, began, ends, GraphCarry{}, lane);
     else
-        search_graph_frames<4>(src, T, first, S, phonemes, stay, initial, final_, arc_begin + first, in_lds, out_totals,
-                               out_begins, stage, dist, began, ends, lane);
+        search_graph_frames<4, false>(src, T, first, S, phonemes, stay, initial, final_, arc_begin + first, in_lds,
+                                      out_totals, out_begins, stage, dist, began, ends, GraphCarry{}, lane);
+}
+
+// ---- live phrase search over a phoneme graph (ppg_search_graph_stream_*) ----
+//
+// ppg_search_graph carried across the pushes of a stream, as ppg_search_stream_* carries ppg_search.  One pair is a
+// stream and a graph; every graph runs on every stream.  The curve is the recurrence above, unchanged, with a fresh
+// start at frame t of a push at position p beginning at p + t; the detector, flush and reset are the live search's
+// (Detector, Events, emit and detect in front of search_strips), word for word.  The caller owns the state: five blocks,
+// each 256-byte aligned: the position of every stream (int32), the verdict of viterbi_check on every graph (int32,
+// written once, at open), the detector of every pair (8 words), then D and b of every pair: a row of 64 words where
+// max_states <= 64 and of 256 above, so that a row is loaded and stored without a mask.  The positions, the detectors
+// and the rows lie as the live search's do, so its three small kernels serve here as they are: search_stream_advance
+// after the programme (the only writer of a position in a push), search_stream_flush, and search_stream_reset with
+// max_states in the place of max_phonemes.  One kernel of its own:
+//   search_graph_stream_programme  grid (graphs, streams), one wave per pair: search_graph_frames<G, Live = true>, the
+//                                  body of search_graph_programme between a load and a store of the row.  A push goes by
+//                                  the verdict stored at open and checks nothing of the graph again, so whatever the
+//                                  arrays hold by now, S is held inside [1, row], the arcs inside the held block, and a
+//                                  source is clamped into [0, S) where it is copied to LDS: the only place the kernel
+//                                  takes one from (ppg_viterbi_stream_push's rule).
+
+struct SearchGraphStreamLayout {
+    size_t positions, verdict, detectors, totals, begins, bytes;       // byte offsets into the state
+};
+
+// (65535 x 65535 pairs of 256 states are 4.4e12 bytes per block: inside a size_t)
+inline SearchGraphStreamLayout search_graph_stream_layout(int streams, int graphs, int max_states) {
+    SearchGraphStreamLayout w{};
+    const size_t pairs = (size_t)streams * graphs, states = stream_states(max_states);
+    size_t at = 0;
+    w.positions = at; at = align256(at + (size_t)streams * sizeof(int));
+    w.verdict = at; at = align256(at + (size_t)graphs * sizeof(int));
+    w.detectors = at; at = align256(at + pairs * sizeof(Detector));
+    w.totals = at; at = align256(at + pairs * states * sizeof(float));
+    w.begins = at; at = align256(at + pairs * states * sizeof(int));
+    w.bytes = at;
+    return w;
+}
+
+bool search_graph_stream_sizes_fine(int streams, int graphs, int max_states) {
+    return streams > 0 && streams <= PPG_SEARCH_MAX_ITEMS && graphs > 0 && graphs <= PPG_SEARCH_MAX_QUERIES &&
+           max_states > 0 && max_states <= PPG_VITERBI_MAX_STATES;
+}
+
+// the checks every entry of the live search over graphs shares: the state and its geometry
+int check_search_graph_stream_state(const char* what, const void* state, int streams, int graphs, int max_states) {
+    if (!state || streams <= 0 || graphs <= 0 || max_states <= 0)
+        return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (!search_graph_stream_sizes_fine(streams, graphs, max_states))
+        return ppg::fail_message(PPG_EINVAL, "%s: %d streams, %d graphs and %d states: at most %d streams, %d graphs "
+                                 "and %d states per graph", what, streams, graphs, max_states, PPG_SEARCH_MAX_ITEMS,
+                                 PPG_SEARCH_MAX_QUERIES, PPG_VITERBI_MAX_STATES);
+    if (reinterpret_cast<uintptr_t>(state) % 16)
+        return ppg::fail_message(PPG_EINVAL, "%s: the state must be 16-byte aligned", what);
+    return PPG_OK;
+}
+
+// grid (graphs, streams), 64 threads, `held` * 8 bytes of dynamic LDS; `row` = stream_states(max_states).  count = -1
+// for a pair that cannot be pushed (its graph refused at open or beyond 256 states or 4096 arcs, its length outside
+// [0, frames], a position that would pass INT32_MAX), which touches nothing else; every other pair gets the events of
+// this push, sentinels behind them, and its state moved on by lengths[stream] frames.
+__global__ __launch_bounds__(64) void search_graph_stream_programme(
+    const float* __restrict__ logp, int frames, const int* __restrict__ lengths, const int* __restrict__ verdict,
+    const int* __restrict__ state_begin, const int* __restrict__ phonemes, const float* __restrict__ stay,
+    const float* __restrict__ initial, const float* __restrict__ final_, const int* __restrict__ arc_begin,
+    const int* __restrict__ sources, const float* __restrict__ weights, int held, int row,
+    const int* __restrict__ positions, Detector* __restrict__ detectors, float* __restrict__ state_totals,
+    int* __restrict__ state_begins, float threshold, int patience, int cap, int* __restrict__ begin,
+    int* __restrict__ end, float* __restrict__ total, float* __restrict__ mean, int* __restrict__ count,
+    float* __restrict__ curve_total, int* __restrict__ curve_begin)
+{
+    __shared__ float4 stage[2][CHUNK_VEC];
+    __shared__ __attribute__((aligned(16))) float dist[2][GSTATES];
+    __shared__ __attribute__((aligned(16))) int began[2][GSTATES];
+    __shared__ SearchGraphEnds ends;
+    extern __shared__ uint2 held_arcs[];
+    const int g = blockIdx.x, item = blockIdx.y, lane = threadIdx.x;
+    const size_t pair = (size_t)item * gridDim.x + g;
+    const int T = lengths[item], base = positions[item];
+    bool fine = T >= 0 && T <= frames && base >= 0 && T <= INT32_MAX - base && verdict[g] != 0;
+    int first = 0, S = 0, arc0 = 0, arcs = 0;
+    if (fine) {                                                // (uniform) a good verdict: the graph's indices were sound
+        first = state_begin[g];
+        S = state_begin[g + 1] - first;
+        fine = S >= 1 && S <= row;                             // (row <= GSTATES)
+    }
+    if (fine) {
+        arc0 = arc_begin[first];
+        arcs = arc_begin[first + S] - arc0;
+        fine = arcs >= 0 && arcs <= held;                      // (held <= PPG_SEARCH_GRAPH_MAX_ARCS: the dynamic LDS)
+    }
+    if (!fine) {                                               // (uniform)
+        if (lane == 0) count[pair] = -1;
+        return;
+    }
+    // what is written now and then by one lane, or once at the end: out of the scalar file, which the frames need
+    Events out{in_vector_registers(begin + pair * cap), in_vector_registers(end + pair * cap),
+               in_vector_registers(total + pair * cap), in_vector_registers(mean + pair * cap), cap, 0};
+    Detector* my_detector = in_vector_registers(detectors + pair);
+    int* my_count = in_vector_registers(count + pair);
+    if (T > 0) {                                               // (uniform) a stream with no frames sits out the step
+        for (int i = lane; i < arcs; i += 64)
+            held_arcs[i] = make_uint2((uint32_t)min(max(sources[arc0 + i], 0), S - 1),
+                                      __float_as_uint(weights[arc0 + i]));
+        __syncthreads();                                       // a lane keeps its states' first arcs: it reads them now
+        const float4* src = reinterpret_cast<const float4*>(logp + (size_t)item * frames * PREP);
+        const ViterbiArcs<true> in_lds{held_arcs, nullptr, nullptr, arcs};
+        float* out_totals = curve_total ? curve_total + pair * frames : nullptr;
+        int* out_begins = curve_total ? curve_begin + pair * frames : nullptr;
+        Detector det = *my_detector;                           // (every lane reads it; lane 0 uses it)
+        const GraphCarry live{in_vector_registers(state_totals + pair * row),
+                              in_vector_registers(state_begins + pair * row), base, &det, &out, threshold, patience};
+        if (S <= 64)
+            search_graph_frames<1, true>(src, T, first, S, phonemes, stay, initial, final_, arc_begin + first, in_lds,
+                                         out_totals, out_begins, stage, dist, began, ends, live, lane);
+        else
+            search_graph_frames<4, true>(src, T, first, S, phonemes, stay, initial, final_, arc_begin + first, in_lds,
+                                         out_totals, out_begins, stage, dist, began, ends, live, lane);
+        if (lane == 0) *my_detector = det;
+    }
+    const int events = __builtin_amdgcn_readfirstlane(out.count);
+    if (lane == 0) *my_count = events;
+    for (int h = min(events, cap) + lane; h < cap; h += 64) {
+        out.begin[h] = out.end[h] = -1;
+        out.total[h] = out.mean[h] = NAN;
+    }
 }
 
 }  // namespace
@@ -3529,18 +3713,8 @@ int ppg_search_graph(int device, const float* ppg, int frames, int items, const 
     const char* what = "search_graph";
     if (const int rc = check_common(what, ppg, frames, items, lengths, PPG_SEARCH_MAX_FRAMES, PPG_SEARCH_MAX_ITEMS))
         return rc;
-    if (!workspace || graphs <= 0 || n_states <= 0 || n_arcs < 0 || max_states <= 0)
-        return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
-    if (graphs > PPG_SEARCH_MAX_QUERIES)
-        return ppg::fail_message(PPG_EINVAL, "%s: %d graphs, at most %d per call", what, graphs, PPG_SEARCH_MAX_QUERIES);
-    if (max_states > PPG_VITERBI_MAX_STATES)
-        return ppg::fail_message(PPG_EINVAL, "%s: %d states, at most %d per graph", what, max_states,
-                                 PPG_VITERBI_MAX_STATES);
-    if (n_states < graphs || (long long)n_states > (long long)graphs * max_states ||
-        (long long)n_arcs > (long long)graphs * PPG_VITERBI_MAX_ARCS)
-        return ppg::fail_message(PPG_EINVAL, "%s: %d states and %d arcs cannot be %d graphs of 1 to %d states and at "
-                                 "most %d arcs", what, n_states, n_arcs, graphs, max_states, PPG_VITERBI_MAX_ARCS);
-    if (n_arcs > 0 && (!sources || !weights)) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (!workspace) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (const int rc = check_search_graphs(what, graphs, n_states, n_arcs, max_states, sources, weights)) return rc;
     if (const int rc = check_words(what, {state_begin, state_phonemes, stay, initial, final_, arc_begin, begin, end,
                                           total, mean, count},
                                    {sources, weights, curve_total, curve_begin, ppg, lengths}))
@@ -3570,6 +3744,117 @@ int ppg_search_graph(int device, const float* ppg, int frames, int items, const 
                        weights, totals, begins, ones, count);
     hipLaunchKernelGGL(search_pick, dim3(graphs, items), dim3(64), 0, s, frames, lengths, ones, top, threshold, totals,
                        begins, begin, end, total, mean, count, curve_total, curve_begin);
+    return launched(what);
+}
+
+size_t ppg_search_graph_stream_state_bytes(int streams, int graphs, int max_states) {
+    return search_graph_stream_sizes_fine(streams, graphs, max_states)
+               ? search_graph_stream_layout(streams, graphs, max_states).bytes : 0;
+}
+
+size_t ppg_search_graph_stream_workspace_bytes(int streams, int frames, int graphs) {
+    if (streams <= 0 || streams > PPG_SEARCH_MAX_ITEMS || frames <= 0 || frames > PPG_SEARCH_MAX_FRAMES ||
+        graphs <= 0 || graphs > PPG_SEARCH_MAX_QUERIES)
+        return 0;
+    return prepared_bytes(streams, frames);
+}
+
+int ppg_search_graph_stream_open(int device, void* state, int streams, int graphs, int n_states, int n_arcs,
+                                 int max_states, const int32_t* state_begin, const int32_t* state_phonemes,
+                                 const float* stay, const float* initial, const float* final_,
+                                 const int32_t* arc_begin, const int32_t* sources, const float* weights,
+                                 void* stream) {
+    const char* what = "search_graph_stream_open";
+    if (const int rc = check_search_graph_stream_state(what, state, streams, graphs, max_states)) return rc;
+    if (const int rc = check_search_graphs(what, graphs, n_states, n_arcs, max_states, sources, weights)) return rc;
+    if (const int rc = check_words(what, {state_begin, state_phonemes, stay, initial, final_, arc_begin},
+                                   {sources, weights}))
+        return rc;
+    if (const int rc = select_device(device)) return rc;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const SearchGraphStreamLayout w = search_graph_stream_layout(streams, graphs, max_states);
+    char* st = static_cast<char*>(state);
+    hipLaunchKernelGGL(viterbi_check, dim3(graphs), dim3(64), 0, s, n_states, n_arcs, max_states, state_begin,
+                       state_phonemes, stay, initial, final_, arc_begin, sources, weights,
+                       reinterpret_cast<int*>(st + w.verdict));
+    hipLaunchKernelGGL(search_stream_reset, dim3(graphs, streams), dim3(64), 0, s, max_states,
+                       static_cast<const int*>(nullptr), reinterpret_cast<int*>(st + w.positions),
+                       reinterpret_cast<Detector*>(st + w.detectors), reinterpret_cast<float*>(st + w.totals),
+                       reinterpret_cast<int*>(st + w.begins));
+    return launched(what);
+}
+
+int ppg_search_graph_stream_reset(int device, void* state, int streams, int graphs, int max_states,
+                                  const int32_t* which, void* stream) {
+    const char* what = "search_graph_stream_reset";
+    if (const int rc = check_search_graph_stream_state(what, state, streams, graphs, max_states)) return rc;
+    if (const int rc = check_words(what, {}, {which})) return rc;
+    if (const int rc = select_device(device)) return rc;
+    const SearchGraphStreamLayout w = search_graph_stream_layout(streams, graphs, max_states);
+    char* st = static_cast<char*>(state);
+    hipLaunchKernelGGL(search_stream_reset, dim3(graphs, streams), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       max_states, which, reinterpret_cast<int*>(st + w.positions),
+                       reinterpret_cast<Detector*>(st + w.detectors), reinterpret_cast<float*>(st + w.totals),
+                       reinterpret_cast<int*>(st + w.begins));
+    return launched(what);
+}
+
+int ppg_search_graph_stream_push(int device, void* state, const float* ppg, int frames, int streams,
+                                 const int32_t* lengths, int graphs, int n_states, int n_arcs, int max_states,
+                                 const int32_t* state_begin, const int32_t* state_phonemes, const float* stay,
+                                 const float* initial, const float* final_, const int32_t* arc_begin,
+                                 const int32_t* sources, const float* weights, float threshold, int patience, int cap,
+                                 int32_t* begin, int32_t* end, float* total, float* mean, int32_t* count,
+                                 float* curve_total, int32_t* curve_begin, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    const char* what = "search_graph_stream_push";
+    if (!ppg || !lengths || !workspace || frames <= 0) return ppg::fail_message(PPG_EINVAL, "%s: bad argument", what);
+    if (const int rc = check_search_graph_stream_state(what, state, streams, graphs, max_states)) return rc;
+    if (const int rc = check_search_graphs(what, graphs, n_states, n_arcs, max_states, sources, weights)) return rc;
+    if (frames > PPG_SEARCH_MAX_FRAMES)
+        return ppg::fail_message(PPG_EINVAL, "%s: %d frames, at most %d", what, frames, PPG_SEARCH_MAX_FRAMES);
+    if (const int rc = check_words(what, {state_begin, state_phonemes, stay, initial, final_, arc_begin, begin, end,
+                                          total, mean, count},
+                                   {sources, weights, curve_total, curve_begin, ppg, lengths}))
+        return rc;
+    if (threshold != threshold) return ppg::fail_message(PPG_EINVAL, "%s: the threshold is NaN", what);
+    if (patience < 0) return ppg::fail_message(PPG_EINVAL, "%s: patience = %d is negative", what, patience);
+    if (cap < 1) return ppg::fail_message(PPG_EINVAL, "%s: cap = %d, must be at least 1", what, cap);
+    if (!curve_total != !curve_begin)
+        return ppg::fail_message(PPG_EINVAL, "%s: curve_total and curve_begin go together", what);
+    if (const int rc = check_workspace(what, workspace, workspace_bytes, prepared_bytes(streams, frames))) return rc;
+    if (const int rc = select_device(device)) return rc;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const SearchGraphStreamLayout w = search_graph_stream_layout(streams, graphs, max_states);
+    char* st = static_cast<char*>(state);
+    int* positions = reinterpret_cast<int*>(st + w.positions);
+    float* logp = static_cast<float*>(workspace);
+    const int held = n_arcs < VHELD ? n_arcs : VHELD;         // the arcs a wave keeps in LDS, as in ppg_search_graph
+    hipLaunchKernelGGL(align_prepare, dim3((frames + 63) / 64, streams), dim3(64), 0, s, ppg, frames, lengths, logp);
+    hipLaunchKernelGGL(search_graph_stream_programme, dim3(graphs, streams), dim3(64), (size_t)held * sizeof(uint2), s,
+                       logp, frames, lengths, reinterpret_cast<const int*>(st + w.verdict), state_begin, state_phonemes,
+                       stay, initial, final_, arc_begin, sources, weights, held, stream_states(max_states), positions,
+                       reinterpret_cast<Detector*>(st + w.detectors), reinterpret_cast<float*>(st + w.totals),
+                       reinterpret_cast<int*>(st + w.begins), threshold, patience, cap, begin, end, total, mean, count,
+                       curve_total, curve_begin);
+    hipLaunchKernelGGL(search_stream_advance, dim3((streams + 63) / 64), dim3(64), 0, s, streams, frames, lengths,
+                       positions);
+    return launched(what);
+}
+
+int ppg_search_graph_stream_flush(int device, void* state, int streams, int graphs, int max_states,
+                                  const int32_t* which, int32_t* begin, int32_t* end, float* total, float* mean,
+                                  int32_t* count, void* stream) {
+    const char* what = "search_graph_stream_flush";
+    if (const int rc = check_search_graph_stream_state(what, state, streams, graphs, max_states)) return rc;
+    if (const int rc = check_words(what, {begin, end, total, mean, count}, {which})) return rc;
+    if (const int rc = select_device(device)) return rc;
+    const SearchGraphStreamLayout w = search_graph_stream_layout(streams, graphs, max_states);
+    const size_t pairs = (size_t)streams * graphs;
+    hipLaunchKernelGGL(search_stream_flush, dim3((unsigned)((pairs + 63) / 64)), dim3(64), 0,
+                       static_cast<hipStream_t>(stream), streams, graphs, which,
+                       reinterpret_cast<Detector*>(static_cast<char*>(state) + w.detectors), begin, end, total, mean,
+                       count);
     return launched(what);
 }
 

@@ -212,6 +212,23 @@ SYMBOLS = {
     'ppg_search_stream_flush': (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_search_graph_stream_state_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_search_graph_stream_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ppg_search_graph_stream_open': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_search_graph_stream_reset': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'ppg_search_graph_stream_push': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_int,
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'ppg_search_graph_stream_flush': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'ppg_recognize_stream_state_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     'ppg_recognize_stream_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     'ppg_recognize_stream_reset': (ctypes.c_int, [
@@ -1439,6 +1456,81 @@ def search_stream_flush(state, streams, queries, most, which=None):
             device.index, state.data_ptr(), streams, queries, most, which.data_ptr() if which is not None else None,
             begin.data_ptr(), end.data_ptr(), total.data_ptr(), mean.data_ptr(), count.data_ptr(),
             torch.cuda.current_stream().cuda_stream))
+    return begin, end, total, mean, count
+
+
+def search_graph_stream_state(device, streams, packed):
+    """The device block of a live search over graphs (ppg_search_graph_stream_*), opened: `streams` streams x the
+    graphs of `packed` (a PackedGraphs of contiguous int32 / fp32 tensors on `device`, as the live Viterbi takes it).
+    uint8; its owner passes it to the calls below with the same numbers and the same `packed`."""
+    size = library().ppg_search_graph_stream_state_bytes(streams, packed.graphs, packed.max_states)
+    if size == 0:
+        raise ValueError(f'a live search over graphs takes 1 to {SEARCH_MAX_ITEMS} streams, 1 to '
+                         f'{SEARCH_GRAPH_MAX_GRAPHS} graphs and 1 to {VITERBI_MAX_STATES} states, got {streams}, '
+                         f'{packed.graphs} and {packed.max_states}')
+    state = torch.empty((size,), dtype=torch.uint8, device=device)
+    search_graph_stream_open(state, streams, packed)
+    return state
+
+
+def search_graph_stream_open(state, streams, packed):
+    """ppg_search_graph_stream_open on the current stream: the device checks the graphs, keeps its verdicts in the
+    state, and every stream starts at frame 0."""
+    with torch.cuda.device(state.device):
+        _check(library().ppg_search_graph_stream_open(
+            state.device.index, state.data_ptr(), streams, *_graph_arguments(packed),
+            torch.cuda.current_stream().cuda_stream))
+
+
+def search_graph_stream_reset(state, streams, graphs, max_states, which=None):
+    """ppg_search_graph_stream_reset on the current stream: `which` is None (all) or a device int32 (streams,) of
+    flags."""
+    with torch.cuda.device(state.device):
+        _check(library().ppg_search_graph_stream_reset(
+            state.device.index, state.data_ptr(), streams, graphs, max_states,
+            which.data_ptr() if which is not None else None, torch.cuda.current_stream().cuda_stream))
+
+
+def search_graph_stream_push(state, ppg, lengths, packed, threshold, patience, cap, workspace, want_curve=False):
+    """ppg_search_graph_stream_push on the current stream: ppg (streams, 40, frames) fp32 and lengths (streams,) int32,
+    contiguous on the state's device; `packed` the graphs the state was opened with; workspace a uint8 tensor there ->
+    the outputs of search_stream_push with the graphs in the place of the queries."""
+    device = state.device
+    streams, frames = ppg.shape[0], ppg.shape[2]
+    shape = (streams, packed.graphs, cap)
+    begin = torch.empty(shape, dtype=torch.int32, device=device)
+    end = torch.empty(shape, dtype=torch.int32, device=device)
+    total = torch.empty(shape, dtype=torch.float32, device=device)
+    mean = torch.empty(shape, dtype=torch.float32, device=device)
+    count = torch.empty((streams, packed.graphs), dtype=torch.int32, device=device)
+    curve = None
+    if want_curve:
+        curve = (torch.full((streams, packed.graphs, frames), -math.inf, dtype=torch.float32, device=device),
+                 torch.full((streams, packed.graphs, frames), -1, dtype=torch.int32, device=device))
+    with torch.cuda.device(device):
+        _check(library().ppg_search_graph_stream_push(
+            device.index, state.data_ptr(), ppg.data_ptr(), frames, streams, lengths.data_ptr(),
+            *_graph_arguments(packed), threshold, patience, cap, begin.data_ptr(), end.data_ptr(), total.data_ptr(),
+            mean.data_ptr(), count.data_ptr(), curve[0].data_ptr() if curve else None,
+            curve[1].data_ptr() if curve else None, workspace.data_ptr(), workspace.numel(),
+            torch.cuda.current_stream().cuda_stream))
+    return begin, end, total, mean, count, curve
+
+
+def search_graph_stream_flush(state, streams, graphs, max_states, which=None):
+    """ppg_search_graph_stream_flush on the current stream -> begin, end int32, total, mean fp32 (streams, graphs, 1)
+    and count (streams, graphs) int32: 1 where a hit was pending."""
+    device = state.device
+    begin = torch.empty((streams, graphs, 1), dtype=torch.int32, device=device)
+    end = torch.empty((streams, graphs, 1), dtype=torch.int32, device=device)
+    total = torch.empty((streams, graphs, 1), dtype=torch.float32, device=device)
+    mean = torch.empty((streams, graphs, 1), dtype=torch.float32, device=device)
+    count = torch.empty((streams, graphs), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _check(library().ppg_search_graph_stream_flush(
+            device.index, state.data_ptr(), streams, graphs, max_states,
+            which.data_ptr() if which is not None else None, begin.data_ptr(), end.data_ptr(), total.data_ptr(),
+            mean.data_ptr(), count.data_ptr(), torch.cuda.current_stream().cuda_stream))
     return begin, end, total, mean, count
 
 
